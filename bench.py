@@ -26,6 +26,16 @@ rank and freeze the partition layout under test). Launch:
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N ...            # N GPUs
 
+A plain run sets up, warms up, times the steps and prints the result line.
+--full adds the one check the headline figure does not need: the HIP payload
+kernel run inside the last warmup pod's partition. --dump-outputs DIR writes
+the last timed step's allocation (placement + realized partition, one row
+per rank) to DIR/allocation.npy; with the same arguments the profile
+sequence is seeded, so two builds can be compared output for output.
+A single-rank run keeps its processes inside one L3 cache domain (recorded
+in config.cpu_affinity; --no-pin turns it off): where the scheduler places
+them otherwise decides a quarter of the figure from one run to the next.
+
 Weak scaling: per-GPU work is fixed (each rank drives K pods at its node);
 value = total pods / max-over-ranks elapsed seconds.
 """
@@ -259,6 +269,127 @@ def run_payload(pod_env: dict, warm_pool: bool = False) -> None:
             f"{out.stdout} {out.stderr}")
 
 
+def _parse_cpu_list(text: str) -> set:
+    """`0-7,128-135` -> {0..7, 128..135} (the kernel's cpulist format)."""
+    cpus: set = set()
+    for part in text.strip().split(","):
+        if not part:
+            continue
+        lo, _, hi = part.partition("-")
+        cpus.update(range(int(lo), int(hi or lo) + 1))
+    return cpus
+
+
+def _format_cpu_list(cpus: set) -> str:
+    """{0..7, 128..135} -> `0-7,128-135`."""
+    runs: list = []
+    for c in sorted(cpus):
+        if runs and c == runs[-1][1] + 1:
+            runs[-1][1] = c
+        else:
+            runs.append([c, c])
+    return ",".join(f"{a}-{b}" if b > a else str(a) for a, b in runs)
+
+
+def pin_to_l3_domain(min_cpus: int = 4):
+    """Keep this process, and the control plane and store daemon it spawns,
+    on the CPUs that share an L3 cache with the one we are running on.
+
+    One step is a chain of cross-process wakeups. On a many-socket, many-CCX
+    host the scheduler scatters the three processes differently in every
+    run, and a wakeup that crosses an L3 domain or a socket costs several
+    times one that does not: measured on a 256-CPU MI355X host, identical
+    runs spread 650-920 pods/s unpinned and 966-1007 pods/s inside one
+    domain (profiles/bench_cpu_pinning.md). Returns the cpulist pinned to, or None where nothing was done
+    (no such topology information, or fewer than `min_cpus` CPUs of the
+    domain are allowed to us)."""
+    try:
+        allowed = os.sched_getaffinity(0)
+        with open("/proc/self/stat") as f:
+            # field 39 (processor); fields after the ")" start at field 3
+            cpu = int(f.read().rsplit(")", 1)[1].split()[36])
+        cache = f"/sys/devices/system/cpu/cpu{cpu}/cache"
+        domain = None
+        for idx in sorted(os.listdir(cache)):
+            if not idx.startswith("index"):
+                continue
+            with open(os.path.join(cache, idx, "level")) as f:
+                if f.read().strip() != "3":
+                    continue
+            with open(os.path.join(cache, idx, "shared_cpu_list")) as f:
+                domain = _parse_cpu_list(f.read()) & allowed
+        if domain is None or len(domain) < min_cpus or domain == allowed:
+            return None
+        # every thread that exists already (imports may have started some);
+        # threads and children created from here on inherit
+        for tid in os.listdir("/proc/self/task"):
+            os.sched_setaffinity(int(tid), domain)
+    except (AttributeError, OSError, ValueError, IndexError) as e:
+        log.warning("cpu pinning skipped: %s", e)
+        return None
+    return _format_cpu_list(domain)
+
+
+def capture_allocation(cr: dict, pod_name: str, into: dict) -> None:
+    """Pick `pod_name`'s allocation (the controller's placement) and its
+    prepared partition (what the node agent realized) out of a node CR."""
+    spec = cr.get("spec", {})
+    for alloc in (spec.get("allocations") or {}).values():
+        if alloc.get("podName") != pod_name:
+            continue
+        into["allocation"] = alloc
+        for prep in (spec.get("prepared") or {}).values():
+            if prep.get("podUUID") == alloc.get("podUUID"):
+                into["prepared"] = prep
+
+
+# columns of allocation.npy, one row per rank
+ALLOCATION_COLUMNS = (
+    "ordinal", "start_xcd", "size_xcds", "target_partitions_per_gpu",
+    "target_memory_domains", "realized_partitions_per_gpu",
+    "realized_memory_domains", "realized_xcds", "realized_memory_gb",
+    "device_index",
+)
+
+
+def allocation_row(captured: dict) -> list:
+    """The last timed step's output as numbers: the placement the controller
+    chose and the partition the agent realized for it. Modes are encoded by
+    their partition / memory-domain counts (SPX=1 .. CPX=8, NPSn=n)."""
+    from instaslice_amd.partition.profiles import ComputeMode, MemoryMode
+
+    if "allocation" not in captured or "prepared" not in captured:
+        raise RuntimeError(
+            "--dump-outputs: the last timed step's allocation was never "
+            f"observed (got {sorted(captured)})")
+    a, p = captured["allocation"], captured["prepared"]
+
+    # a mode the model does not know (or none reported) encodes as 0
+    def parts(mode: str) -> float:
+        known = mode in ComputeMode._value2member_map_
+        return float(ComputeMode(mode).num_partitions) if known else 0.0
+
+    def domains(mode: str) -> float:
+        known = mode in MemoryMode._value2member_map_
+        return float(MemoryMode(mode).num_domains) if known else 0.0
+
+    return [
+        float(a["ordinal"]), float(a["start"]), float(a["size"]),
+        parts(a.get("computeMode", "")), domains(a.get("memoryMode", "")),
+        parts(p["computeMode"]), domains(p["memoryMode"]),
+        float(p["xcds"]), float(p["memoryGB"]), float(p.get("deviceIndex", 0)),
+    ]
+
+
+def dump_outputs(out_dir: str, rows: list) -> None:
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arr = np.asarray(rows, dtype=np.float64).reshape(len(rows),
+                                                     len(ALLOCATION_COLUMNS))
+    np.save(os.path.join(out_dir, "allocation.npy"), arr)
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -279,9 +410,21 @@ def main() -> int:
                     help="skip HIP payload validation entirely")
     ap.add_argument("--payload-every", type=int, default=0,
                     help="run the payload inside every Nth pod's partition "
-                         "during timed steps (0 = validate once after warmup; "
-                         "sleep pods per BASELINE.json otherwise)")
+                         "during timed steps (0 = sleep pods per "
+                         "BASELINE.json; --full validates once after warmup)")
     ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step produced (the partition handed to its pod) "
+                         "as DIR/<name>.npy, float64")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks the headline figure does not "
+                         "need: the HIP payload validation inside the last "
+                         "warmup pod's partition")
+    ap.add_argument("--no-pin", action="store_true",
+                    help="leave CPU placement to the scheduler (a single-"
+                         "rank run otherwise keeps its processes inside "
+                         "one L3 cache domain)")
     args = ap.parse_args()
 
     # the lifecycle chain is thread-wakeup bound; don't let a CPU-holding
@@ -290,6 +433,13 @@ def main() -> int:
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
+
+    # a single-rank run is three processes (this one, the control plane, the
+    # store daemon) that fit one L3 domain; multi-rank topologies need more
+    # cores than a domain has and stay with the scheduler
+    cpu_affinity = None
+    if world == 1 and not args.no_pin:
+        cpu_affinity = pin_to_l3_domain()
 
     # stdout carries EXACTLY one JSON line (the driver parses it). Gloo's
     # C++ context prints a "[Gloo] Rank N is connected..." banner straight
@@ -419,10 +569,18 @@ def main() -> int:
             if pred(ev[0], ev[1]):
                 return
 
-    def step(i: int, record: bool) -> None:
+    # --dump-outputs: what the last timed step hands its pod, picked off the
+    # node-CR events the step already receives (a store read inside the
+    # timed window only if the pod's ungate overtakes them, see step())
+    last_step = args.warmup + args.steps - 1
+    captured: dict = {}
+
+    def step(i: int, record: bool, rng: random.Random = rng) -> None:
         name = f"bench-r{rank}-{i}"
         prof = rng.choice(profiles)
         from instaslice_amd.api.types import new_pod
+
+        capture = record and i == last_step and args.dump_outputs is not None
 
         t0 = time.perf_counter()
         store.create(new_pod(name, profile=prof,
@@ -430,6 +588,9 @@ def main() -> int:
                              labels=bench_label))
 
         def scheduled(et, obj):
+            if capture and obj["kind"] == "Instaslice":
+                capture_allocation(obj, name, captured)
+                return False
             return (obj["kind"] == "Pod"
                     and obj["metadata"]["name"] == name
                     and not obj["spec"].get("schedulingGates"))
@@ -437,8 +598,15 @@ def main() -> int:
         wait_event(scheduled, f"pod {name} ({prof}) scheduled")
         if record:
             latencies_ms.append((time.perf_counter() - t0) * 1000.0)
+        if capture and "prepared" not in captured:
+            # the pod's ungate overtook the node-CR event: read the CR itself
+            # (the one store round-trip the dump can add, once per run)
+            capture_allocation(
+                store.get("Instaslice", node, "instaslice-system"),
+                name, captured)
         run_pl = payload_on and (
-            (not record and i == args.warmup - 1)  # validate once at warmup end
+            # --full: validate once at warmup end
+            (args.full and not record and i == args.warmup - 1)
             or (record and args.payload_every > 0 and i % args.payload_every == 0)
         )
         if run_pl:
@@ -474,8 +642,11 @@ def main() -> int:
     # 6 s closes the measured cold-start gap (557 -> 824 across
     # back-to-back runs was ~6 s of lifecycles; the old 2 s left the
     # driver's short windows ~25% under full-window numbers)
+    # its own generator: how many lifecycles fit in the window varies from
+    # run to run, and must not shift the seeded sequence of the W + N steps
+    init_rng = random.Random(args.seed + rank + 104729)
     while time.perf_counter() - t_init < 6.0 and i_init < 5000:
-        step(-1 - i_init, record=False)
+        step(-1 - i_init, record=False, rng=init_rng)
         i_init += 1
 
     for i in range(args.warmup):
@@ -511,6 +682,17 @@ def main() -> int:
     else:
         all_lat = latencies_ms
 
+    if args.dump_outputs is not None:
+        # gather what each rank saw first and judge it afterwards: a rank
+        # that raised before the collective would leave the others blocked
+        seen = [captured]
+        if world > 1:
+            seen = [None] * world
+            dist.all_gather_object(seen, captured)
+        rows = [allocation_row(c) for c in seen]
+        if rank == 0:
+            dump_outputs(args.dump_outputs, rows)
+
     n_gpus = world if world > 1 else args.gpus
     if rank == 0:
         total_pods = args.steps * world
@@ -537,6 +719,7 @@ def main() -> int:
             # numbers WITH this flag, not alongside full-window ones.
             "short_window": args.steps < 100,
             "max_rank_rss_mb": round(rss_mb, 1),
+            "latency_samples": len(all_lat),  # one per timed step and rank
             "p50_alloc_latency_ms": round(p50, 3) if p50 is not None else None,
             "p99_alloc_latency_ms": round(p99, 3) if p99 is not None else None,
             "config": {
@@ -547,7 +730,10 @@ def main() -> int:
                 "profile_mix": profiles,
                 "partitioning": partitioning,
                 "backend": backend_name,
-                "payload_kernel": payload_on,
+                "payload_kernel": payload_on and (
+                    args.full or args.payload_every > 0),
+                "full": args.full,
+                "cpu_affinity": cpu_affinity,
                 "payload_every": args.payload_every,
                 "policy": args.policy,
             },

@@ -497,6 +497,14 @@ _fuzz_env = {}
 _fuzz_n = [0]
 
 
+def _stop_fuzz_backends():
+    for key in ("py", "nat"):
+        _fuzz_env[key].close()
+    for server in _fuzz_env["servers"]:
+        server.stop()
+    _fuzz_env.clear()
+
+
 def _fuzz_backends():
     """Shared servers for the differential fuzz (per-example server spawn
     exhausted fds/threads at high example counts)."""
@@ -506,6 +514,11 @@ def _fuzz_backends():
         _fuzz_env["servers"] = (py_server, nat_server)
         _fuzz_env["py"] = NetStoreClient("127.0.0.1", py_server.port)
         _fuzz_env["nat"] = NetStoreClient("127.0.0.1", nat_server.port)
+        # shared for the whole session, so stopped when the interpreter
+        # exits: the daemon is a child process and would outlive the run
+        import atexit
+
+        atexit.register(_stop_fuzz_backends)
     return _fuzz_env["py"], _fuzz_env["nat"]
 
 
