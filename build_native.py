@@ -95,18 +95,19 @@ def build(force: bool = False) -> None:
     # 3. _payload pybind module (gfx950 device code)
     src = ops_dir / "csrc" / "payload_pybind.hip"
     hdr = ops_dir / "csrc" / "payload_core.hpp"
+    hdr_gemm = ops_dir / "csrc" / "payload_gemm.hpp"  # included by payload_core
     out = ops_dir / f"_payload{EXT}"
-    if force or not newer(out, [src, hdr], ARCH):
+    if force or not newer(out, [src, hdr, hdr_gemm], ARCH):
         run([HIPCC, f"--offload-arch={ARCH}", "-shared", *common,
              *pybind_includes(), src, "-o", out])
-        record_hash(out, [src, hdr], ARCH)
+        record_hash(out, [src, hdr, hdr_gemm], ARCH)
 
     # 4. instaslice-payload standalone workload binary
     src = ops_dir / "csrc" / "payload_main.hip"
     out = bin_dir / "instaslice-payload"
-    if force or not newer(out, [src, hdr], ARCH):
+    if force or not newer(out, [src, hdr, hdr_gemm], ARCH):
         run([HIPCC, f"--offload-arch={ARCH}", *common, src, "-o", out])
-        record_hash(out, [src, hdr], ARCH)
+        record_hash(out, [src, hdr, hdr_gemm], ARCH)
 
     # 5. instaslice-stored: native store daemon (plain host C++, g++ —
     # no ROCm dependency; runs on any node incl. the CPU test tier)

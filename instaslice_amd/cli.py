@@ -18,7 +18,10 @@
     python -m instaslice_amd describe   --store HOST:PORT --name P
     python -m instaslice_amd top        --store HOST:PORT [--interval S]
     python -m instaslice_amd cordon     --store HOST:PORT --node N [--uncordon]
-    python -m instaslice_amd payload    [info|vecadd|membw|busy|census] ...
+    python -m instaslice_amd payload    [info|vecadd|membw|busy|census|gemm|
+                                         verify] ...
+    python -m instaslice_amd verify     --profile NAME
+                                        [--visible-devices UUID_OR_INDEX]
 
 NODE_NAME env is honored for the daemonset (downward-API parity with
 config/manager/manager.yaml's fieldRef env).
@@ -360,6 +363,23 @@ def cmd_payload(args) -> int:
     return subprocess.call([bin_path] + args.payload_args)
 
 
+def cmd_verify(args) -> int:
+    """Run the payload probes inside the visible partition and judge them
+    against the requested profile; prints the judged JSON, exit 0 iff ok."""
+    from instaslice_amd.ops import verify
+
+    env = {}
+    if args.visible_devices is not None:
+        env["ROCR_VISIBLE_DEVICES"] = args.visible_devices
+    try:
+        verdict = verify.run(args.profile, env=env)
+    except ValueError as e:
+        verdict = {"ok": False, "failed": [], "profile": args.profile,
+                   "reason": str(e), "report": None}
+    print(json.dumps(verdict))
+    return 0 if verdict["ok"] else 1
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="instaslice-amd")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -456,6 +476,15 @@ def main(argv=None) -> int:
     p = sub.add_parser("payload", help="run the HIP payload binary")
     p.add_argument("payload_args", nargs="*", default=["info"])
     p.set_defaults(fn=cmd_payload)
+
+    p = sub.add_parser("verify",
+                       help="probe the visible partition, judge it against "
+                            "a profile")
+    p.add_argument("--profile", required=True, help="e.g. cpx-1x36")
+    p.add_argument("--visible-devices", default=None,
+                   help="ROCR_VISIBLE_DEVICES for the probe (partition UUID "
+                        "or index); default: inherit the environment")
+    p.set_defaults(fn=cmd_verify)
 
     args = ap.parse_args(argv)
     return args.fn(args)

@@ -14,6 +14,8 @@
 //                CPX partition exactly one XCD may appear; in SPX all 8.
 //                (XCC_ID read is a validation/performance tool, never a
 //                correctness dependency — cdna_hip_programming.md §1.)
+//   gemm         bf16 MFMA GEMM, exact-checked and timed: the matrix cores are
+//                what a tenant pays for (payload_gemm.hpp, included below)
 //
 // Kernel style per the CDNA4 playbook: 256-thread blocks (4 waves of 64),
 // float4 (dwordx4) streaming accesses for coalescing, grid-strided loops
@@ -262,3 +264,6 @@ inline int device_count() {
 }
 
 }  // namespace payload
+
+// bf16 MFMA GEMM payload: uses HIP_CHECK and kBlock from above
+#include "payload_gemm.hpp"

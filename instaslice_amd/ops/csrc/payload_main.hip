@@ -10,6 +10,18 @@
 //   instaslice-payload membw [BYTES] [ITERS]
 //   instaslice-payload busy [MS]
 //   instaslice-payload census
+//   instaslice-payload gemm [M N K [ITERS]]   bf16 MFMA GEMM, exact-checked
+//                                             and timed (default 4096 4096
+//                                             1024, 10 iters; K <= 1024);
+//                                             exit 1 unless max_err == 0
+//   instaslice-payload verify [XCDS]          census + vecadd + gemm check +
+//                                             membw + timed gemm in one JSON
+//                                             line; XCDS (0 or absent: not
+//                                             checked) is the XCD count the
+//                                             partition should show. Only
+//                                             vecadd, gemm and xcds are
+//                                             judged; rates are reported.
+//                                             exit 1 iff "failed" is non-empty
 //   instaslice-payload serve      (persistent worker: commands on stdin,
 //                                  one JSON line per command on stdout —
 //                                  HIP init is paid once, so a warm pool
@@ -21,6 +33,7 @@
 //
 // Build: see build_native.py (hipcc --offload-arch=gfx950).
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -31,6 +44,9 @@
 #include "payload_core.hpp"
 
 using namespace payload;
+
+// JSON has no inf/nan: an error that is not finite prints as a huge number
+static double json_num(double v) { return std::isfinite(v) ? v : 1e300; }
 
 int main(int argc, char** argv) {
   const char* cmd = argc > 1 ? argv[1] : "info";
@@ -75,9 +91,54 @@ int main(int argc, char** argv) {
       for (unsigned v : c)
         if (v) ++xcds;
       std::printf("], \"xcds_visible\": %d}\n", xcds);
+    } else if (std::strcmp(cmd, "gemm") == 0) {
+      int m = argc > 4 ? std::atoi(argv[2]) : 4096;
+      int n = argc > 4 ? std::atoi(argv[3]) : 4096;
+      int k = argc > 4 ? std::atoi(argv[4]) : 1024;
+      int iters = argc > 5 ? std::atoi(argv[5]) : 10;
+      GemmResult r = run_gemm(m, n, k, iters);
+      bool ok = r.max_err == 0.0;
+      std::printf(
+          "{\"ok\": %s, \"cmd\": \"gemm\", \"m\": %d, \"n\": %d, \"k\": %d, "
+          "\"iters\": %d, \"tflops\": %.2f, \"max_err\": %g}\n",
+          ok ? "true" : "false", m, n, k, iters, r.tflops, json_num(r.max_err));
+      return ok ? 0 : 1;
+    } else if (std::strcmp(cmd, "verify") == 0) {
+      int expected = argc > 2 ? std::atoi(argv[2]) : 0;
+      DeviceInfo info = get_device_info(0);
+      auto census = run_xcd_census();
+      int xcds = 0;
+      for (unsigned v : census)
+        if (v) ++xcds;
+      double vecadd_err = run_vecadd(1 << 20);
+      double gemm_err = run_gemm_check(96, 160, 224);
+      double gbs = run_membw(size_t{256} << 20, 5);
+      GemmResult r = run_gemm(4096, 4096, 1024, 5);
+      if (r.max_err > gemm_err) gemm_err = r.max_err;
+      bool bad_vecadd = vecadd_err != 0.0;
+      bool bad_gemm = gemm_err != 0.0;
+      bool bad_xcds = expected > 0 && xcds != expected;
+      bool ok = !(bad_vecadd || bad_gemm || bad_xcds);
+      std::printf("{\"ok\": %s, \"cmd\": \"verify\", \"xcds_expected\": %d, "
+                  "\"xcds_visible\": %d, \"per_xcd\": [",
+                  ok ? "true" : "false", expected, xcds);
+      for (int i = 0; i < 8; ++i) std::printf("%s%u", i ? ", " : "", census[i]);
+      int per = xcds > 0 ? xcds : 1;
+      std::printf(
+          "], \"cu_count\": %d, \"total_mem_gb\": %.1f, \"vecadd_max_err\": %g, "
+          "\"gemm_max_err\": %g, \"gb_per_s\": %.1f, \"tflops\": %.2f, "
+          "\"gb_per_s_per_xcd\": %.1f, \"tflops_per_xcd\": %.2f, \"failed\": [",
+          info.cu_count, info.total_mem_gb, json_num(vecadd_err),
+          json_num(gemm_err), gbs, r.tflops, gbs / per, r.tflops / per);
+      const char* sep = "";
+      if (bad_vecadd) { std::printf("%s\"vecadd\"", sep); sep = ", "; }
+      if (bad_gemm) { std::printf("%s\"gemm\"", sep); sep = ", "; }
+      if (bad_xcds) { std::printf("%s\"xcds\"", sep); sep = ", "; }
+      std::printf("]}\n");
+      return ok ? 0 : 1;
     } else if (std::strcmp(cmd, "serve") == 0) {
       // warm-pool worker: one line per request, one JSON line per reply
-      //   vecadd <n> | busy <ms> | ping | quit
+      //   vecadd <n> | busy <ms> | gemm [M N K] | ping | quit
       std::string line;
       while (std::getline(std::cin, line)) {
         std::istringstream iss(line);
@@ -95,6 +156,14 @@ int main(int argc, char** argv) {
             std::printf(
                 "{\"ok\": %s, \"cmd\": \"vecadd\", \"n\": %zu, \"max_err\": %g}\n",
                 err == 0.0 ? "true" : "false", n, err);
+          } else if (verb == "gemm") {
+            int m = 96, n = 160, k = 224, tm, tn, tk;
+            if (iss >> tm >> tn >> tk) { m = tm; n = tn; k = tk; }
+            double err = run_gemm_check(m, n, k);
+            std::printf(
+                "{\"ok\": %s, \"cmd\": \"gemm\", \"m\": %d, \"n\": %d, "
+                "\"k\": %d, \"max_err\": %g}\n",
+                err == 0.0 ? "true" : "false", m, n, k, json_num(err));
           } else if (verb == "busy") {
             double ms = 10.0;
             iss >> ms;

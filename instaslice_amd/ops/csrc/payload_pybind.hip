@@ -2,6 +2,7 @@
 // Built in-tree as instaslice_amd/ops/_payload*.so by build_native.py
 // (hipcc --offload-arch=gfx950). Fails loudly at call time if no GPU.
 
+#include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
@@ -10,7 +11,7 @@
 namespace py = pybind11;
 
 PYBIND11_MODULE(_payload, m) {
-  m.doc() = "gfx950 HIP payload kernels (vecadd / membw / busy / xcd census)";
+  m.doc() = "gfx950 HIP payload kernels (vecadd / membw / busy / xcd census / gemm)";
 
   m.def("device_count", &payload::device_count,
         "Number of visible HIP devices (0 if no GPU/driver)");
@@ -70,4 +71,81 @@ PYBIND11_MODULE(_payload, m) {
         return d;
       },
       py::arg("device") = 0);
+
+  // float32 arrays convert through forcecast | c_style: a non-contiguous or
+  // other-dtype array is copied into a contiguous float32 one, and anything
+  // that cannot be converted is a TypeError
+  using f32_array = py::array_t<float, py::array::c_style | py::array::forcecast>;
+
+  m.def(
+      "to_bf16",
+      [](f32_array x) {
+        py::array_t<uint16_t> out(
+            std::vector<py::ssize_t>(x.shape(), x.shape() + x.ndim()));
+        const float* src = x.data();
+        uint16_t* dst = out.mutable_data();
+        for (py::ssize_t i = 0, n = x.size(); i < n; ++i)
+          dst[i] = payload::to_bf16_rne(src[i]);
+        return out;
+      },
+      py::arg("x"),
+      "float32 -> bf16 bits (uint16), round-to-nearest-even; host only, no GPU");
+
+  m.def(
+      "gemm_bf16",
+      [](f32_array a, f32_array b, int device) {
+        if (a.ndim() != 2 || b.ndim() != 2)
+          throw py::value_error("gemm_bf16: a and b must be 2-D");
+        if (a.shape(1) != b.shape(0))
+          throw py::value_error("gemm_bf16: a is (M,K) and b is (K,N): K differs");
+        if (a.shape(0) < 1 || a.shape(1) < 1 || b.shape(1) < 1)
+          throw py::value_error("gemm_bf16: empty operand");
+        if (a.shape(0) > INT32_MAX || a.shape(1) > INT32_MAX ||
+            b.shape(1) > INT32_MAX)
+          throw py::value_error("gemm_bf16: shape too large");
+        int M = static_cast<int>(a.shape(0)), K = static_cast<int>(a.shape(1)),
+            N = static_cast<int>(b.shape(1));
+        py::array_t<float> c({static_cast<py::ssize_t>(M), static_cast<py::ssize_t>(N)});
+        const float* pa = a.data();
+        const float* pb = b.data();
+        float* pc = c.mutable_data();
+        {
+          py::gil_scoped_release rel;
+          payload::gemm_bf16(pa, pb, pc, M, N, K, device);
+        }
+        return c;
+      },
+      py::arg("a"), py::arg("b"), py::arg("device") = 0,
+      "C (M,N) float32 = bf16(a (M,K)) @ bf16(b (K,N)) on the MFMA kernel");
+
+  m.def(
+      "run_gemm_check",
+      [](int mm, int n, int k, int device) {
+        py::gil_scoped_release rel;
+        return payload::run_gemm_check(mm, n, k, device);
+      },
+      py::arg("m"), py::arg("n"), py::arg("k"), py::arg("device") = 0,
+      "integer-pattern GEMM vs host int64 reference; returns max abs error "
+      "(expect 0); K <= 1024");
+
+  m.def(
+      "run_gemm",
+      [](int mm, int n, int k, int iters, int device) {
+        payload::GemmResult r;
+        {
+          py::gil_scoped_release rel;
+          r = payload::run_gemm(mm, n, k, iters, device);
+        }
+        py::dict d;
+        d["m"] = mm;
+        d["n"] = n;
+        d["k"] = k;
+        d["iters"] = iters;
+        d["tflops"] = r.tflops;
+        d["max_err"] = r.max_err;
+        return d;
+      },
+      py::arg("m") = 4096, py::arg("n") = 4096, py::arg("k") = 1024,
+      py::arg("iters") = 10, py::arg("device") = 0,
+      "timed bf16 MFMA GEMM, 256 outputs spot-checked exactly; K <= 1024");
 }
