@@ -19,8 +19,11 @@
     python -m instaslice_amd top        --store HOST:PORT [--interval S]
     python -m instaslice_amd cordon     --store HOST:PORT --node N [--uncordon]
     python -m instaslice_amd payload    [info|vecadd|membw|busy|census|gemm|
-                                         verify] ...
+                                         memcheck|verify] ...
     python -m instaslice_amd verify     --profile NAME
+                                        [--visible-devices UUID_OR_INDEX]
+    python -m instaslice_amd memcheck   --profile NAME [--gb G | --fraction F]
+                                        [--passes N]
                                         [--visible-devices UUID_OR_INDEX]
 
 NODE_NAME env is honored for the daemonset (downward-API parity with
@@ -380,6 +383,26 @@ def cmd_verify(args) -> int:
     return 0 if verdict["ok"] else 1
 
 
+def cmd_memcheck(args) -> int:
+    """Sweep a buffer of the visible partition's memory with the memcheck
+    payload and judge it against the requested profile; prints the judged
+    JSON, exit 0 iff ok."""
+    from instaslice_amd.ops import verify
+
+    env = {}
+    if args.visible_devices is not None:
+        env["ROCR_VISIBLE_DEVICES"] = args.visible_devices
+    try:
+        verdict = verify.run_memcheck(args.profile, env=env, gb=args.gb,
+                                      fraction=args.fraction,
+                                      passes=args.passes)
+    except ValueError as e:
+        verdict = {"ok": False, "failed": [], "profile": args.profile,
+                   "reason": str(e), "report": None}
+    print(json.dumps(verdict))
+    return 0 if verdict["ok"] else 1
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="instaslice-amd")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -485,6 +508,22 @@ def main(argv=None) -> int:
                    help="ROCR_VISIBLE_DEVICES for the probe (partition UUID "
                         "or index); default: inherit the environment")
     p.set_defaults(fn=cmd_verify)
+
+    p = sub.add_parser("memcheck",
+                       help="sweep the visible partition's memory, judge it "
+                            "against a profile")
+    p.add_argument("--profile", required=True, help="e.g. cpx-1x36")
+    size = p.add_mutually_exclusive_group()
+    size.add_argument("--gb", type=float, default=None,
+                      help="buffer size in GiB (default 1; stay well above "
+                           "0.25, the Infinity Cache, to reach HBM)")
+    size.add_argument("--fraction", type=float, default=None,
+                      help="buffer size as a fraction of the profile's memory")
+    p.add_argument("--passes", type=int, default=1)
+    p.add_argument("--visible-devices", default=None,
+                   help="ROCR_VISIBLE_DEVICES for the probe (partition UUID "
+                        "or index); default: inherit the environment")
+    p.set_defaults(fn=cmd_memcheck)
 
     args = ap.parse_args(argv)
     return args.fn(args)

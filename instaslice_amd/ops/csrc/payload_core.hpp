@@ -16,6 +16,10 @@
 //                correctness dependency — cdna_hip_programming.md §1.)
 //   gemm         bf16 MFMA GEMM, exact-checked and timed: the matrix cores are
 //                what a tenant pays for (payload_gemm.hpp, included below)
+//   memcheck     moving-inversions memory test with an address-derived
+//                pattern at streaming rate: the HBM a profile promises is
+//                there, holds data and does not alias (payload_memcheck.hpp,
+//                included below)
 //
 // Kernel style per the CDNA4 playbook: 256-thread blocks (4 waves of 64),
 // float4 (dwordx4) streaming accesses for coalescing, grid-strided loops
@@ -267,3 +271,6 @@ inline int device_count() {
 
 // bf16 MFMA GEMM payload: uses HIP_CHECK and kBlock from above
 #include "payload_gemm.hpp"
+
+// memcheck payload: also uses grid_for, detail::DeviceBuffer and detail::Event
+#include "payload_memcheck.hpp"

@@ -14,6 +14,16 @@
 //                                             and timed (default 4096 4096
 //                                             1024, 10 iters; K <= 1024);
 //                                             exit 1 unless max_err == 0
+//   instaslice-payload memcheck [BYTES [PASSES [FLIP_OFFSET FLIP_MASK]]]
+//                                             moving-inversions memory test
+//                                             of one BYTES buffer (default
+//                                             1 GiB, 1 pass); FLIP_* corrupt
+//                                             one word once (self-test);
+//                                             "beyond_llc" says whether BYTES
+//                                             exceeds the 256 MiB Infinity
+//                                             Cache (below it the run proves
+//                                             the kernel, not the HBM);
+//                                             exit 1 iff bad_words != 0
 //   instaslice-payload verify [XCDS]          census + vecadd + gemm check +
 //                                             membw + timed gemm in one JSON
 //                                             line; XCDS (0 or absent: not
@@ -47,6 +57,23 @@ using namespace payload;
 
 // JSON has no inf/nan: an error that is not finite prints as a huge number
 static double json_num(double v) { return std::isfinite(v) ? v : 1e300; }
+
+// one JSON line for a memcheck result; bad_bits is a string because a u64
+// does not survive a JSON double
+static bool print_memcheck(const MemcheckResult& r) {
+  bool ok = r.bad_words == 0;
+  std::printf(
+      "{\"ok\": %s, \"cmd\": \"memcheck\", \"bytes\": %zu, \"passes\": %d, "
+      "\"bad_words\": %llu, \"first_bad_offset\": %lld, \"bad_bits\": \"0x%llx\", "
+      "\"fill_gb_per_s\": %.1f, \"check_gb_per_s\": %.1f, \"ms\": %.3f, "
+      "\"beyond_llc\": %s}\n",
+      ok ? "true" : "false", r.bytes, r.passes,
+      static_cast<unsigned long long>(r.bad_words),
+      static_cast<long long>(r.first_bad_offset),
+      static_cast<unsigned long long>(r.bad_bits), r.fill_gb_s, r.check_gb_s,
+      r.ms, r.bytes > kMemcheckLlcBytes ? "true" : "false");
+  return ok;
+}
 
 int main(int argc, char** argv) {
   const char* cmd = argc > 1 ? argv[1] : "info";
@@ -103,6 +130,13 @@ int main(int argc, char** argv) {
           "\"iters\": %d, \"tflops\": %.2f, \"max_err\": %g}\n",
           ok ? "true" : "false", m, n, k, iters, r.tflops, json_num(r.max_err));
       return ok ? 0 : 1;
+    } else if (std::strcmp(cmd, "memcheck") == 0) {
+      size_t bytes = argc > 2 ? std::strtoull(argv[2], nullptr, 10) : (size_t{1} << 30);
+      int passes = argc > 3 ? std::atoi(argv[3]) : 1;
+      int64_t flip_offset = argc > 5 ? std::strtoll(argv[4], nullptr, 10) : -1;
+      uint64_t flip_mask = argc > 5 ? std::strtoull(argv[5], nullptr, 0) : 0;
+      return print_memcheck(run_memcheck(bytes, passes, 0, 0, flip_offset, flip_mask))
+                 ? 0 : 1;
     } else if (std::strcmp(cmd, "verify") == 0) {
       int expected = argc > 2 ? std::atoi(argv[2]) : 0;
       DeviceInfo info = get_device_info(0);
@@ -138,7 +172,7 @@ int main(int argc, char** argv) {
       return ok ? 0 : 1;
     } else if (std::strcmp(cmd, "serve") == 0) {
       // warm-pool worker: one line per request, one JSON line per reply
-      //   vecadd <n> | busy <ms> | gemm [M N K] | ping | quit
+      //   vecadd <n> | busy <ms> | gemm [M N K] | memcheck [BYTES] | ping | quit
       std::string line;
       while (std::getline(std::cin, line)) {
         std::istringstream iss(line);
@@ -164,6 +198,10 @@ int main(int argc, char** argv) {
                 "{\"ok\": %s, \"cmd\": \"gemm\", \"m\": %d, \"n\": %d, "
                 "\"k\": %d, \"max_err\": %g}\n",
                 err == 0.0 ? "true" : "false", m, n, k, json_num(err));
+          } else if (verb == "memcheck") {
+            size_t bytes = size_t{64} << 20;
+            iss >> bytes;
+            print_memcheck(run_memcheck(bytes));
           } else if (verb == "busy") {
             double ms = 10.0;
             iss >> ms;

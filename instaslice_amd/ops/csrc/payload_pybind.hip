@@ -11,7 +11,8 @@
 namespace py = pybind11;
 
 PYBIND11_MODULE(_payload, m) {
-  m.doc() = "gfx950 HIP payload kernels (vecadd / membw / busy / xcd census / gemm)";
+  m.doc() = "gfx950 HIP payload kernels (vecadd / membw / busy / xcd census / gemm / "
+            "memcheck)";
 
   m.def("device_count", &payload::device_count,
         "Number of visible HIP devices (0 if no GPU/driver)");
@@ -148,4 +149,63 @@ PYBIND11_MODULE(_payload, m) {
       py::arg("m") = 4096, py::arg("n") = 4096, py::arg("k") = 1024,
       py::arg("iters") = 10, py::arg("device") = 0,
       "timed bf16 MFMA GEMM, 256 outputs spot-checked exactly; K <= 1024");
+
+  m.def(
+      "memcheck_pattern",
+      [](uint64_t first_word, size_t n_words, uint64_t seed) {
+        py::array_t<uint64_t> out(static_cast<py::ssize_t>(n_words));
+        payload::memcheck_pattern(out.mutable_data(), first_word, n_words, seed);
+        return out;
+      },
+      py::arg("first_word"), py::arg("n_words"), py::arg("seed") = 0,
+      "the memcheck pattern's 64-bit words first_word .. first_word+n_words-1 "
+      "(uint64); host only, no GPU");
+
+  m.def(
+      "memcheck_fill",
+      [](size_t bytes, uint64_t seed, uint64_t base_unit, bool invert, int device,
+         int blocks) {
+        if (bytes < payload::kMemcheckUnit)
+          throw py::value_error("memcheck_fill: bytes must be >= 16");
+        py::array_t<uint64_t> out(
+            static_cast<py::ssize_t>(bytes / payload::kMemcheckUnit * 2));
+        uint64_t* dst = out.mutable_data();
+        {
+          py::gil_scoped_release rel;
+          payload::memcheck_fill(dst, bytes, seed, base_unit, invert, device, blocks);
+        }
+        return out;
+      },
+      py::arg("bytes"), py::arg("seed") = 0, py::arg("base_unit") = 0,
+      py::arg("invert") = false, py::arg("device") = 0, py::arg("blocks") = 0,
+      "run the memcheck fill kernel alone on a fresh buffer and return its "
+      "bytes // 16 * 2 words (uint64); base_unit is the pattern index of unit 0");
+
+  m.def(
+      "run_memcheck",
+      [](size_t bytes, int passes, int device, int blocks, int64_t flip_offset,
+         uint64_t flip_mask) {
+        payload::MemcheckResult r;
+        {
+          py::gil_scoped_release rel;
+          r = payload::run_memcheck(bytes, passes, device, blocks, flip_offset,
+                                    flip_mask);
+        }
+        py::dict d;
+        d["bytes"] = r.bytes;
+        d["passes"] = r.passes;
+        d["bad_words"] = r.bad_words;
+        d["first_bad_offset"] = r.first_bad_offset;
+        d["bad_bits"] = py::int_(r.bad_bits);
+        d["fill_gb_s"] = r.fill_gb_s;
+        d["check_gb_s"] = r.check_gb_s;
+        d["ms"] = r.ms;
+        return d;
+      },
+      py::arg("bytes") = (size_t{1} << 30), py::arg("passes") = 1,
+      py::arg("device") = 0, py::arg("blocks") = 0, py::arg("flip_offset") = -1,
+      py::arg("flip_mask") = 0,
+      "moving-inversions memory test of one buffer: fill, check + invert, "
+      "check, per pass; flip_offset / flip_mask corrupt one word once (self-test). "
+      "Buffers of 256 MiB or less can be served from the Infinity Cache");
 }

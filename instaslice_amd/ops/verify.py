@@ -17,6 +17,16 @@ never judged: there are no measured per-partition values to hold them to.
 A live verifier holds the device for its run (a second or two), which blocks
 partition mode flips for that long: run it after a partition is handed over,
 not while the agent is re-carving the GPU.
+
+Memory has a probe of its own. `run_memcheck` runs `instaslice-payload
+memcheck` (a moving-inversions test with an address-derived pattern) over one
+buffer sized in GiB or as a fraction of the profile's own memory, and
+`judge_memcheck` fails "memory" unless the whole requested size was swept and
+no word came back wrong. A partition that cannot allocate the size comes back
+`ok: False` with the HIP error as the reason. The chip has a 256 MiB Infinity
+Cache: a buffer of that size or less can be served back from cache, so such a
+run proves the kernel, not the HBM (the report's `beyond_llc` says which it
+was). Operational runs should be well above 256 MiB.
 """
 
 from __future__ import annotations
@@ -108,5 +118,109 @@ def run(profile_name: str, env: Optional[Dict[str, str]] = None,
         verdict["ok"] = False
         verdict["reason"] = f"payload exited {proc.returncode}"
     elif proc.returncode != 0:
+        verdict["reason"] = f"payload exited {proc.returncode}"
+    return verdict
+
+
+# ---- memcheck ---------------------------------------------------------------
+
+GIB = 1 << 30  # a profile's "GB" is 2^30 bytes, as in the report's total_mem_gb
+
+# One child: hipMalloc of the buffer, four traversals per pass, exit.
+# Measured once on an MI355X in SPX (profiles/memcheck_probe.md): 128 GiB, one
+# pass, 3.58 s wall for the whole child, of which 0.086 s between upload and
+# result; the rest is process start, hipMalloc and teardown (32 GiB: 1.39 s,
+# 2 GiB: 0.4 s). Scaled linearly, 0.9 of spx-8x288 is about 7.5 s and a further
+# pass about 0.2 s, so 120 s leaves more than a tenfold margin.
+MEMCHECK_TIMEOUT_S = 120.0
+
+
+def _is_count(value) -> bool:
+    return isinstance(value, int) and not isinstance(value, bool)
+
+
+def judge_memcheck(report: dict, profile_name: str, want_bytes: int) -> dict:
+    """Judge an `instaslice-payload memcheck` report: "memory" fails unless
+    the whole of `want_bytes` (rounded down to 16) was swept at least once and
+    no word came back wrong. Pure; the report's own `ok` is not trusted.
+    ValueError on a profile name that does not parse."""
+    parse_profile_name(profile_name)
+    clean = (_is_zero(report.get("bad_words"))
+             and _is_count(report.get("first_bad_offset"))
+             and report["first_bad_offset"] == -1
+             and _is_count(report.get("bytes"))
+             and report["bytes"] == int(want_bytes) // 16 * 16
+             and _is_count(report.get("passes"))
+             and report["passes"] >= 1)
+    failed = [] if clean else ["memory"]
+    return {"ok": not failed, "failed": failed, "profile": profile_name,
+            "report": report}
+
+
+def memcheck_bytes(profile_name: str, gb: Optional[float] = None,
+                   fraction: Optional[float] = None) -> int:
+    """Buffer size for a memcheck of this profile: `gb` GiB, or `fraction` of
+    the profile's own memory, rounded down to 16 bytes; 1 GiB when neither is
+    given. ValueError on both, on a non-positive size and on a bad name."""
+    _mode, _xcds, profile_gb = parse_profile_name(profile_name)
+    if gb is not None and fraction is not None:
+        raise ValueError("give at most one of gb and fraction")
+    if fraction is not None:
+        if not 0 < fraction <= 1:
+            raise ValueError(f"fraction must be in (0, 1], got {fraction!r}")
+        size = fraction * profile_gb * GIB
+    else:
+        size = (1 if gb is None else gb) * GIB
+    nbytes = int(size) // 16 * 16
+    if nbytes < 16:
+        raise ValueError("memcheck size must be at least 16 bytes")
+    return nbytes
+
+
+def run_memcheck(profile_name: str, env: Optional[Dict[str, str]] = None,
+                 gb: Optional[float] = None, fraction: Optional[float] = None,
+                 passes: int = 1, runner: Callable = subprocess.run) -> dict:
+    """Run `instaslice-payload memcheck` in a fresh child with `env` and judge
+    its report, with the same contract as `run`. The buffer is `gb` GiB or
+    `fraction` of the profile's own memory (fraction=0.9 on cpx-1x36 demands
+    that 32.4 GiB be allocatable and hold data); default 1 GiB. A child that
+    cannot allocate comes back `ok: False` with the HIP error in `reason`.
+    ValueError on a bad profile name, on both gb and fraction, and on
+    passes < 1."""
+    want_bytes = memcheck_bytes(profile_name, gb=gb, fraction=fraction)
+    if not _is_count(passes) or passes < 1:
+        raise ValueError(f"passes must be an integer >= 1, got {passes!r}")
+    child_env = dict(os.environ)
+    child_env.update({k: str(v) for k, v in (env or {}).items()})
+    try:
+        proc = runner([BIN_PATH, "memcheck", str(want_bytes), str(passes)],
+                      capture_output=True, text=True,
+                      timeout=MEMCHECK_TIMEOUT_S, env=child_env)
+    except FileNotFoundError:
+        return _not_run(profile_name, f"payload binary not found: {BIN_PATH}")
+    except subprocess.TimeoutExpired:
+        return _not_run(profile_name,
+                        f"memcheck timed out after {MEMCHECK_TIMEOUT_S:.0f} s")
+    except OSError as e:
+        return _not_run(profile_name, f"could not start payload binary: {e}")
+
+    lines = [ln for ln in (proc.stdout or "").splitlines() if ln.strip()]
+    try:
+        report = json.loads(lines[-1]) if lines else None
+    except ValueError:
+        report = None
+    if not isinstance(report, dict):
+        tail = (proc.stdout or "").strip()[-200:]
+        return _not_run(profile_name,
+                        f"non-JSON output (exit {proc.returncode}): {tail!r}")
+    if "bad_words" not in report:
+        # the binary's catch-all error line: {"ok": false, "error": "..."}
+        return _not_run(profile_name,
+                        f"memcheck failed (exit {proc.returncode}): "
+                        f"{report.get('error', 'no report fields')}", report)
+    verdict = judge_memcheck(report, profile_name, want_bytes)
+    if proc.returncode != 0:
+        # clean-looking fields do not outvote a non-zero exit
+        verdict["ok"] = False
         verdict["reason"] = f"payload exited {proc.returncode}"
     return verdict
