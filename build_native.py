@@ -97,18 +97,20 @@ def build(force: bool = False) -> None:
     hdr = ops_dir / "csrc" / "payload_core.hpp"
     hdr_gemm = ops_dir / "csrc" / "payload_gemm.hpp"  # included by payload_core
     hdr_memcheck = ops_dir / "csrc" / "payload_memcheck.hpp"  # likewise
+    hdr_mxgemm = ops_dir / "csrc" / "payload_mxgemm.hpp"  # likewise
+    payload_hdrs = [hdr, hdr_gemm, hdr_memcheck, hdr_mxgemm]
     out = ops_dir / f"_payload{EXT}"
-    if force or not newer(out, [src, hdr, hdr_gemm, hdr_memcheck], ARCH):
+    if force or not newer(out, [src, *payload_hdrs], ARCH):
         run([HIPCC, f"--offload-arch={ARCH}", "-shared", *common,
              *pybind_includes(), src, "-o", out])
-        record_hash(out, [src, hdr, hdr_gemm, hdr_memcheck], ARCH)
+        record_hash(out, [src, *payload_hdrs], ARCH)
 
     # 4. instaslice-payload standalone workload binary
     src = ops_dir / "csrc" / "payload_main.hip"
     out = bin_dir / "instaslice-payload"
-    if force or not newer(out, [src, hdr, hdr_gemm, hdr_memcheck], ARCH):
+    if force or not newer(out, [src, *payload_hdrs], ARCH):
         run([HIPCC, f"--offload-arch={ARCH}", *common, src, "-o", out])
-        record_hash(out, [src, hdr, hdr_gemm, hdr_memcheck], ARCH)
+        record_hash(out, [src, *payload_hdrs], ARCH)
 
     # 5. instaslice-stored: native store daemon (plain host C++, g++ —
     # no ROCm dependency; runs on any node incl. the CPU test tier)

@@ -16,6 +16,10 @@
 //                correctness dependency — cdna_hip_programming.md §1.)
 //   gemm         bf16 MFMA GEMM, exact-checked and timed: the matrix cores are
 //                what a tenant pays for (payload_gemm.hpp, included below)
+//   mxgemm       MXFP8 block-scaled MFMA GEMM (OCP e4m3 operands, E8M0 scales
+//                per 32 elements), exact-checked and timed: the low-precision
+//                matrix path, a different instruction and datapath than bf16
+//                (payload_mxgemm.hpp, included below)
 //   memcheck     moving-inversions memory test with an address-derived
 //                pattern at streaming rate: the HBM a profile promises is
 //                there, holds data and does not alias (payload_memcheck.hpp,
@@ -271,6 +275,9 @@ inline int device_count() {
 
 // bf16 MFMA GEMM payload: uses HIP_CHECK and kBlock from above
 #include "payload_gemm.hpp"
+
+// MXFP8 block-scaled MFMA GEMM payload: same helpers, plus the gemm pattern
+#include "payload_mxgemm.hpp"
 
 // memcheck payload: also uses grid_for, detail::DeviceBuffer and detail::Event
 #include "payload_memcheck.hpp"

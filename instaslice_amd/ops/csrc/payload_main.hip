@@ -14,6 +14,12 @@
 //                                             and timed (default 4096 4096
 //                                             1024, 10 iters; K <= 1024);
 //                                             exit 1 unless max_err == 0
+//   instaslice-payload mxgemm [M N K [ITERS]] MXFP8 block-scaled MFMA GEMM
+//                                             (e4m3 operands, E8M0 scales per
+//                                             32 elements), exact-checked and
+//                                             timed (default 4096 4096 2048,
+//                                             10 iters; K <= 2048);
+//                                             exit 1 unless max_err == 0
 //   instaslice-payload memcheck [BYTES [PASSES [FLIP_OFFSET FLIP_MASK]]]
 //                                             moving-inversions memory test
 //                                             of one BYTES buffer (default
@@ -130,6 +136,18 @@ int main(int argc, char** argv) {
           "\"iters\": %d, \"tflops\": %.2f, \"max_err\": %g}\n",
           ok ? "true" : "false", m, n, k, iters, r.tflops, json_num(r.max_err));
       return ok ? 0 : 1;
+    } else if (std::strcmp(cmd, "mxgemm") == 0) {
+      int m = argc > 4 ? std::atoi(argv[2]) : 4096;
+      int n = argc > 4 ? std::atoi(argv[3]) : 4096;
+      int k = argc > 4 ? std::atoi(argv[4]) : 2048;
+      int iters = argc > 5 ? std::atoi(argv[5]) : 10;
+      GemmResult r = run_mxgemm(m, n, k, iters);
+      bool ok = r.max_err == 0.0;
+      std::printf(
+          "{\"ok\": %s, \"cmd\": \"mxgemm\", \"m\": %d, \"n\": %d, \"k\": %d, "
+          "\"iters\": %d, \"tflops\": %.2f, \"max_err\": %g}\n",
+          ok ? "true" : "false", m, n, k, iters, r.tflops, json_num(r.max_err));
+      return ok ? 0 : 1;
     } else if (std::strcmp(cmd, "memcheck") == 0) {
       size_t bytes = argc > 2 ? std::strtoull(argv[2], nullptr, 10) : (size_t{1} << 30);
       int passes = argc > 3 ? std::atoi(argv[3]) : 1;
@@ -172,7 +190,8 @@ int main(int argc, char** argv) {
       return ok ? 0 : 1;
     } else if (std::strcmp(cmd, "serve") == 0) {
       // warm-pool worker: one line per request, one JSON line per reply
-      //   vecadd <n> | busy <ms> | gemm [M N K] | memcheck [BYTES] | ping | quit
+      //   vecadd <n> | busy <ms> | gemm [M N K] | mxgemm [M N K] |
+      //   memcheck [BYTES] | ping | quit
       std::string line;
       while (std::getline(std::cin, line)) {
         std::istringstream iss(line);
@@ -196,6 +215,14 @@ int main(int argc, char** argv) {
             double err = run_gemm_check(m, n, k);
             std::printf(
                 "{\"ok\": %s, \"cmd\": \"gemm\", \"m\": %d, \"n\": %d, "
+                "\"k\": %d, \"max_err\": %g}\n",
+                err == 0.0 ? "true" : "false", m, n, k, json_num(err));
+          } else if (verb == "mxgemm") {
+            int m = 96, n = 160, k = 224, tm, tn, tk;
+            if (iss >> tm >> tn >> tk) { m = tm; n = tn; k = tk; }
+            double err = run_mxgemm_check(m, n, k);
+            std::printf(
+                "{\"ok\": %s, \"cmd\": \"mxgemm\", \"m\": %d, \"n\": %d, "
                 "\"k\": %d, \"max_err\": %g}\n",
                 err == 0.0 ? "true" : "false", m, n, k, json_num(err));
           } else if (verb == "memcheck") {

@@ -6,13 +6,15 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <array>
+
 #include "payload_core.hpp"
 
 namespace py = pybind11;
 
 PYBIND11_MODULE(_payload, m) {
   m.doc() = "gfx950 HIP payload kernels (vecadd / membw / busy / xcd census / gemm / "
-            "memcheck)";
+            "mxgemm / memcheck)";
 
   m.def("device_count", &payload::device_count,
         "Number of visible HIP devices (0 if no GPU/driver)");
@@ -149,6 +151,156 @@ PYBIND11_MODULE(_payload, m) {
       py::arg("m") = 4096, py::arg("n") = 4096, py::arg("k") = 1024,
       py::arg("iters") = 10, py::arg("device") = 0,
       "timed bf16 MFMA GEMM, 256 outputs spot-checked exactly; K <= 1024");
+
+  using u8_array = py::array_t<uint8_t, py::array::c_style | py::array::forcecast>;
+
+  m.def(
+      "to_e4m3",
+      [](f32_array x) {
+        py::array_t<uint8_t> out(
+            std::vector<py::ssize_t>(x.shape(), x.shape() + x.ndim()));
+        const float* src = x.data();
+        uint8_t* dst = out.mutable_data();
+        for (py::ssize_t i = 0, n = x.size(); i < n; ++i)
+          dst[i] = payload::to_e4m3_sat(src[i]);
+        return out;
+      },
+      py::arg("x"),
+      "float32 -> OCP e4m3fn byte (uint8), round-to-nearest-even, saturating at "
+      "+-448; host only, no GPU");
+
+  m.def(
+      "from_e4m3",
+      [](u8_array codes) {
+        py::array_t<float> out(
+            std::vector<py::ssize_t>(codes.shape(), codes.shape() + codes.ndim()));
+        const uint8_t* src = codes.data();
+        float* dst = out.mutable_data();
+        for (py::ssize_t i = 0, n = codes.size(); i < n; ++i)
+          dst[i] = payload::from_e4m3(src[i]);
+        return out;
+      },
+      py::arg("codes"), "OCP e4m3fn byte (uint8) -> float32; host only, no GPU");
+
+  m.def(
+      "mx_quantize",
+      [](f32_array x) {
+        if (x.ndim() < 1)
+          throw py::value_error("mx_quantize: x must have at least one axis");
+        if (x.shape(x.ndim() - 1) < 1 || x.shape(x.ndim() - 1) > INT32_MAX)
+          throw py::value_error("mx_quantize: bad length of the last axis");
+        const int K = static_cast<int>(x.shape(x.ndim() - 1));
+        const py::ssize_t blocks = (K + payload::kMxBlock - 1) / payload::kMxBlock;
+        std::vector<py::ssize_t> shape(x.shape(), x.shape() + x.ndim());
+        py::array_t<uint8_t> codes(shape);
+        shape.back() = blocks;
+        py::array_t<uint8_t> scales(shape);
+        const float* src = x.data();
+        uint8_t* pc = codes.mutable_data();
+        uint8_t* ps = scales.mutable_data();
+        for (py::ssize_t r = 0, rows = x.size() / K; r < rows; ++r)
+          payload::mx_quantize_row(src + r * K, K, pc + r * K, ps + r * blocks);
+        return py::make_tuple(codes, scales);
+      },
+      py::arg("x"),
+      "OCP MX quantization along the last axis: (codes uint8 [..., K], scales "
+      "uint8 [..., ceil(K/32)]), e4m3 elements and E8M0 scales; host only, no GPU");
+
+  // (M, N, K) of an (M,K) x (K,N) product, or ValueError
+  auto mx_dims = [](const char* who, const py::array& a, const py::array& b) {
+    std::string w(who);
+    if (a.ndim() != 2 || b.ndim() != 2)
+      throw py::value_error(w + ": a and b must be 2-D");
+    if (a.shape(1) != b.shape(0))
+      throw py::value_error(w + ": a is (M,K) and b is (K,N): K differs");
+    if (a.shape(0) < 1 || a.shape(1) < 1 || b.shape(1) < 1)
+      throw py::value_error(w + ": empty operand");
+    if (a.shape(0) > INT32_MAX || a.shape(1) > INT32_MAX || b.shape(1) > INT32_MAX)
+      throw py::value_error(w + ": shape too large");
+    return std::array<int, 3>{static_cast<int>(a.shape(0)),
+                              static_cast<int>(b.shape(1)),
+                              static_cast<int>(a.shape(1))};
+  };
+
+  m.def(
+      "gemm_mxfp8",
+      [mx_dims](f32_array a, f32_array b, int device) {
+        auto [M, N, K] = mx_dims("gemm_mxfp8", a, b);
+        py::array_t<float> c({static_cast<py::ssize_t>(M), static_cast<py::ssize_t>(N)});
+        const float* pa = a.data();
+        const float* pb = b.data();
+        float* pc = c.mutable_data();
+        {
+          py::gil_scoped_release rel;
+          payload::gemm_mxfp8(pa, pb, pc, M, N, K, device);
+        }
+        return c;
+      },
+      py::arg("a"), py::arg("b"), py::arg("device") = 0,
+      "C (M,N) float32 = mx(a (M,K)) @ mx(b (K,N)): rows of a and columns of b "
+      "MX-quantized to e4m3 with E8M0 block scales, on the block-scaled MFMA "
+      "kernel; ValueError on a non-finite input");
+
+  m.def(
+      "gemm_mxfp8_raw",
+      [mx_dims](u8_array a_codes, u8_array a_scales, u8_array b_codes,
+                u8_array b_scales, int device) {
+        auto [M, N, K] = mx_dims("gemm_mxfp8_raw", a_codes, b_codes);
+        const py::ssize_t blocks = (K + payload::kMxBlock - 1) / payload::kMxBlock;
+        if (a_scales.ndim() != 2 || a_scales.shape(0) != M ||
+            a_scales.shape(1) != blocks)
+          throw py::value_error("gemm_mxfp8_raw: a_scales must be (M, ceil(K/32))");
+        if (b_scales.ndim() != 2 || b_scales.shape(0) != blocks ||
+            b_scales.shape(1) != N)
+          throw py::value_error("gemm_mxfp8_raw: b_scales must be (ceil(K/32), N)");
+        py::array_t<float> c({static_cast<py::ssize_t>(M), static_cast<py::ssize_t>(N)});
+        const uint8_t* pa = a_codes.data();
+        const uint8_t* psa = a_scales.data();
+        const uint8_t* pb = b_codes.data();
+        const uint8_t* psb = b_scales.data();
+        float* pc = c.mutable_data();
+        {
+          py::gil_scoped_release rel;
+          payload::gemm_mxfp8_raw(pa, psa, pb, psb, pc, M, N, K, device);
+        }
+        return c;
+      },
+      py::arg("a_codes"), py::arg("a_scales"), py::arg("b_codes"),
+      py::arg("b_scales"), py::arg("device") = 0,
+      "C (M,N) float32 from already quantized operands: e4m3 codes (M,K) and "
+      "(K,N), E8M0 scales (M,ceil(K/32)) and (ceil(K/32),N), all uint8");
+
+  m.def(
+      "run_mxgemm_check",
+      [](int mm, int n, int k, int device) {
+        py::gil_scoped_release rel;
+        return payload::run_mxgemm_check(mm, n, k, device);
+      },
+      py::arg("m"), py::arg("n"), py::arg("k"), py::arg("device") = 0,
+      "scaled integer-pattern MXFP8 GEMM vs host int64 reference; returns max "
+      "abs error (expect 0); K <= 2048");
+
+  m.def(
+      "run_mxgemm",
+      [](int mm, int n, int k, int iters, int device) {
+        payload::GemmResult r;
+        {
+          py::gil_scoped_release rel;
+          r = payload::run_mxgemm(mm, n, k, iters, device);
+        }
+        py::dict d;
+        d["m"] = mm;
+        d["n"] = n;
+        d["k"] = k;
+        d["iters"] = iters;
+        d["tflops"] = r.tflops;
+        d["max_err"] = r.max_err;
+        return d;
+      },
+      py::arg("m") = 4096, py::arg("n") = 4096, py::arg("k") = 2048,
+      py::arg("iters") = 10, py::arg("device") = 0,
+      "timed MXFP8 block-scaled MFMA GEMM, 256 outputs spot-checked exactly; "
+      "K <= 2048");
 
   m.def(
       "memcheck_pattern",

@@ -27,6 +27,14 @@ no word came back wrong. A partition that cannot allocate the size comes back
 Cache: a buffer of that size or less can be served back from cache, so such a
 run proves the kernel, not the HBM (the report's `beyond_llc` says which it
 was). Operational runs should be well above 256 MiB.
+
+The low-precision matrix path has a probe of its own too. `run_mxgemm` runs
+`instaslice-payload mxgemm` (the MXFP8 block-scaled MFMA GEMM: e4m3 operands,
+E8M0 scales, exact-checked and timed at 4096 x 4096 x 2048) and `judge_mxgemm`
+fails "mxgemm" unless the maximum error is exactly zero. It exercises a
+different instruction and datapath than the bf16 GEMM that `verify` runs, so a
+partition can pass one and fail the other. Its TFLOP/s is carried in the
+report and never judged.
 """
 
 from __future__ import annotations
@@ -219,6 +227,65 @@ def run_memcheck(profile_name: str, env: Optional[Dict[str, str]] = None,
                         f"memcheck failed (exit {proc.returncode}): "
                         f"{report.get('error', 'no report fields')}", report)
     verdict = judge_memcheck(report, profile_name, want_bytes)
+    if proc.returncode != 0:
+        # clean-looking fields do not outvote a non-zero exit
+        verdict["ok"] = False
+        verdict["reason"] = f"payload exited {proc.returncode}"
+    return verdict
+
+
+# ---- mxgemm -----------------------------------------------------------------
+
+def judge_mxgemm(report: dict, profile_name: str) -> dict:
+    """Judge an `instaslice-payload mxgemm` report: "mxgemm" fails unless
+    `max_err` is a numeric zero and `m`, `n`, `k`, `iters` are integer counts
+    >= 1. `tflops` is carried and never judged. Pure; the report's own `ok`
+    is not trusted. ValueError on a profile name that does not parse."""
+    parse_profile_name(profile_name)
+    clean = (_is_zero(report.get("max_err"))
+             and all(_is_count(report.get(key)) and report[key] >= 1
+                     for key in ("m", "n", "k", "iters")))
+    failed = [] if clean else ["mxgemm"]
+    return {"ok": not failed, "failed": failed, "profile": profile_name,
+            "report": report}
+
+
+def run_mxgemm(profile_name: str, env: Optional[Dict[str, str]] = None,
+               runner: Callable = subprocess.run) -> dict:
+    """Run `instaslice-payload mxgemm` (default shape and iterations) in a
+    fresh child with `env` and judge its report, with the same contract as
+    `run_memcheck`: every way the child can fail comes back as `ok: False`
+    with a `reason`, and only an unparseable profile name raises
+    (ValueError)."""
+    parse_profile_name(profile_name)
+    child_env = dict(os.environ)
+    child_env.update({k: str(v) for k, v in (env or {}).items()})
+    try:
+        proc = runner([BIN_PATH, "mxgemm"], capture_output=True, text=True,
+                      timeout=CHILD_TIMEOUT_S, env=child_env)
+    except FileNotFoundError:
+        return _not_run(profile_name, f"payload binary not found: {BIN_PATH}")
+    except subprocess.TimeoutExpired:
+        return _not_run(profile_name,
+                        f"mxgemm timed out after {CHILD_TIMEOUT_S:.0f} s")
+    except OSError as e:
+        return _not_run(profile_name, f"could not start payload binary: {e}")
+
+    lines = [ln for ln in (proc.stdout or "").splitlines() if ln.strip()]
+    try:
+        report = json.loads(lines[-1]) if lines else None
+    except ValueError:
+        report = None
+    if not isinstance(report, dict):
+        tail = (proc.stdout or "").strip()[-200:]
+        return _not_run(profile_name,
+                        f"non-JSON output (exit {proc.returncode}): {tail!r}")
+    if "max_err" not in report:
+        # the binary's catch-all error line: {"ok": false, "error": "..."}
+        return _not_run(profile_name,
+                        f"mxgemm failed (exit {proc.returncode}): "
+                        f"{report.get('error', 'no report fields')}", report)
+    verdict = judge_mxgemm(report, profile_name)
     if proc.returncode != 0:
         # clean-looking fields do not outvote a non-zero exit
         verdict["ok"] = False
