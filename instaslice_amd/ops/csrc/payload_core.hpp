@@ -24,6 +24,11 @@
 //                pattern at streaming rate: the HBM a profile promises is
 //                there, holds data and does not alias (payload_memcheck.hpp,
 //                included below)
+//   attn         KV-cache decode attention (single-token, grouped-query, head
+//                dim 128) with split-KV: K and V streamed from global memory
+//                straight through the bf16 MFMA with an fp32 online softmax,
+//                exact-checked, bound-checked and timed: the hot kernel of an
+//                LLM server in decode (payload_attn.hpp, included below)
 //
 // Kernel style per the CDNA4 playbook: 256-thread blocks (4 waves of 64),
 // float4 (dwordx4) streaming accesses for coalescing, grid-strided loops
@@ -281,3 +286,6 @@ inline int device_count() {
 
 // memcheck payload: also uses grid_for, detail::DeviceBuffer and detail::Event
 #include "payload_memcheck.hpp"
+
+// decode attention payload: bf16x8, f32x4, to_bf16_rne and the detail helpers
+#include "payload_attn.hpp"

@@ -30,6 +30,20 @@
 //                                             Cache (below it the run proves
 //                                             the kernel, not the HBM);
 //                                             exit 1 iff bad_words != 0
+//   instaslice-payload attn [B HQ HKV L [ITERS [SPLITS]]]
+//                                             KV-cache decode attention (bf16
+//                                             MFMA, fp32 online softmax,
+//                                             split-KV; head dim 128): the
+//                                             self-check at 2 8 2 300 (exact
+//                                             pattern and a dense pattern
+//                                             against fp64), then a timed run
+//                                             (default 32 64 8 4096, 10 iters:
+//                                             512 MiB of K and V per step)
+//                                             with 16 rows checked exactly;
+//                                             SPLITS (0 or absent: auto) fixes
+//                                             the KV split count of the timed
+//                                             run; exit 1 unless max_err == 0
+//                                             and max_rel <= 2^-8
 //   instaslice-payload verify [XCDS]          census + vecadd + gemm check +
 //                                             membw + timed gemm in one JSON
 //                                             line; XCDS (0 or absent: not
@@ -148,6 +162,25 @@ int main(int argc, char** argv) {
           "\"iters\": %d, \"tflops\": %.2f, \"max_err\": %g}\n",
           ok ? "true" : "false", m, n, k, iters, r.tflops, json_num(r.max_err));
       return ok ? 0 : 1;
+    } else if (std::strcmp(cmd, "attn") == 0) {
+      int b = argc > 5 ? std::atoi(argv[2]) : 32;
+      int hq = argc > 5 ? std::atoi(argv[3]) : 64;
+      int hkv = argc > 5 ? std::atoi(argv[4]) : 8;
+      int len = argc > 5 ? std::atoi(argv[5]) : 4096;
+      int iters = argc > 6 ? std::atoi(argv[6]) : 10;
+      int splits = argc > 7 ? std::atoi(argv[7]) : 0;
+      AttnCheck c = run_attn_check(2, 8, 2, 300);
+      AttnResult r = run_attn(b, hq, hkv, len, iters, 0, splits);
+      double max_err = r.max_err > c.max_err ? r.max_err : c.max_err;
+      bool ok = max_err == 0.0 && c.max_rel <= kAttnRelBound;
+      std::printf(
+          "{\"ok\": %s, \"cmd\": \"attn\", \"batch\": %d, \"hq\": %d, "
+          "\"hkv\": %d, \"len\": %d, \"iters\": %d, \"kv_gb_per_s\": %.1f, "
+          "\"steps_per_s\": %.1f, \"tok_per_s\": %.1f, \"max_err\": %g, "
+          "\"max_rel\": %g}\n",
+          ok ? "true" : "false", b, hq, hkv, len, iters, r.kv_gb_s, r.steps_per_s,
+          r.tok_per_s, json_num(max_err), json_num(c.max_rel));
+      return ok ? 0 : 1;
     } else if (std::strcmp(cmd, "memcheck") == 0) {
       size_t bytes = argc > 2 ? std::strtoull(argv[2], nullptr, 10) : (size_t{1} << 30);
       int passes = argc > 3 ? std::atoi(argv[3]) : 1;
@@ -191,7 +224,7 @@ int main(int argc, char** argv) {
     } else if (std::strcmp(cmd, "serve") == 0) {
       // warm-pool worker: one line per request, one JSON line per reply
       //   vecadd <n> | busy <ms> | gemm [M N K] | mxgemm [M N K] |
-      //   memcheck [BYTES] | ping | quit
+      //   attn [B HQ HKV L] | memcheck [BYTES] | ping | quit
       std::string line;
       while (std::getline(std::cin, line)) {
         std::istringstream iss(line);
@@ -225,6 +258,16 @@ int main(int argc, char** argv) {
                 "{\"ok\": %s, \"cmd\": \"mxgemm\", \"m\": %d, \"n\": %d, "
                 "\"k\": %d, \"max_err\": %g}\n",
                 err == 0.0 ? "true" : "false", m, n, k, json_num(err));
+          } else if (verb == "attn") {
+            int b = 2, hq = 8, hkv = 2, len = 300, tb, tq, tk, tl;
+            if (iss >> tb >> tq >> tk >> tl) { b = tb; hq = tq; hkv = tk; len = tl; }
+            AttnCheck c = run_attn_check(b, hq, hkv, len);
+            bool ok = c.max_err == 0.0 && c.max_rel <= kAttnRelBound;
+            std::printf(
+                "{\"ok\": %s, \"cmd\": \"attn\", \"batch\": %d, \"hq\": %d, "
+                "\"hkv\": %d, \"len\": %d, \"max_err\": %g, \"max_rel\": %g}\n",
+                ok ? "true" : "false", b, hq, hkv, len, json_num(c.max_err),
+                json_num(c.max_rel));
           } else if (verb == "memcheck") {
             size_t bytes = size_t{64} << 20;
             iss >> bytes;

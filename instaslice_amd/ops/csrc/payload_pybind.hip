@@ -14,7 +14,7 @@ namespace py = pybind11;
 
 PYBIND11_MODULE(_payload, m) {
   m.doc() = "gfx950 HIP payload kernels (vecadd / membw / busy / xcd census / gemm / "
-            "mxgemm / memcheck)";
+            "mxgemm / memcheck / attn)";
 
   m.def("device_count", &payload::device_count,
         "Number of visible HIP devices (0 if no GPU/driver)");
@@ -360,4 +360,174 @@ PYBIND11_MODULE(_payload, m) {
       "moving-inversions memory test of one buffer: fill, check + invert, "
       "check, per pass; flip_offset / flip_mask corrupt one word once (self-test). "
       "Buffers of 256 MiB or less can be served from the Infinity Cache");
+
+  // ---- decode attention ----------------------------------------------------
+
+  // lengths: None, or B integers in 1 .. L; ValueError otherwise
+  auto attn_lengths = [](const char* who, const py::object& lengths, py::ssize_t B,
+                         py::ssize_t L) {
+    std::vector<int> lens;
+    if (lengths.is_none()) return lens;
+    std::string w(who);
+    py::array_t<int64_t, py::array::c_style | py::array::forcecast> arr;
+    try {
+      arr = py::array_t<int64_t, py::array::c_style | py::array::forcecast>::ensure(
+          lengths);
+    } catch (const py::error_already_set&) {
+      arr = py::array_t<int64_t, py::array::c_style | py::array::forcecast>();
+    }
+    if (!arr) {
+      PyErr_Clear();
+      throw py::value_error(w + ": lengths must be integers");
+    }
+    if (arr.ndim() != 1 || arr.shape(0) != B)
+      throw py::value_error(w + ": lengths must have shape (B,)");
+    for (py::ssize_t b = 0; b < B; ++b) {
+      int64_t v = arr.data()[b];
+      if (v < 1 || v > L) throw py::value_error(w + ": lengths must be in 1 .. L");
+      lens.push_back(static_cast<int>(v));
+    }
+    return lens;
+  };
+
+  // batch, hq, hkv, length of a decode problem, or ValueError
+  auto attn_shape = [](const char* who, py::ssize_t B, py::ssize_t Hq,
+                       py::ssize_t Hkv, py::ssize_t L, int splits) {
+    std::string w(who);
+    if (B < 1 || Hq < 1 || Hkv < 1 || L < 1)
+      throw py::value_error(w + ": empty axis");
+    if (B > 65535 || Hkv > 65535 || Hq > 65535 * 16 || L > (1 << 28))
+      throw py::value_error(w + ": shape too large");
+    if (Hq % Hkv != 0)
+      throw py::value_error(w + ": Hq must be a multiple of Hkv");
+    if (Hq / Hkv > payload::kAttnMaxGroup)
+      throw py::value_error(w + ": Hq / Hkv must be <= 16");
+    if (splits < 0 || splits > payload::kAttnMaxSplits)
+      throw py::value_error(w + ": splits must be in 0 .. 64");
+  };
+
+  m.def(
+      "attn_decode",
+      [attn_lengths, attn_shape](f32_array q, f32_array k, f32_array v,
+                                 py::object lengths, py::object scale, int splits,
+                                 int device) {
+        const char* who = "attn_decode";
+        if (q.ndim() != 3) throw py::value_error("attn_decode: q must be (B,Hq,128)");
+        if (k.ndim() != 4 || v.ndim() != 4)
+          throw py::value_error("attn_decode: k and v must be (B,Hkv,L,128)");
+        if (q.shape(2) != payload::kAttnD || k.shape(3) != payload::kAttnD)
+          throw py::value_error("attn_decode: head dim must be 128");
+        for (int i = 0; i < 4; ++i)
+          if (k.shape(i) != v.shape(i))
+            throw py::value_error("attn_decode: k and v differ in shape");
+        if (k.shape(0) != q.shape(0))
+          throw py::value_error("attn_decode: q and k differ in batch");
+        const py::ssize_t B = q.shape(0), Hq = q.shape(1), Hkv = k.shape(1),
+                          L = k.shape(2);
+        attn_shape(who, B, Hq, Hkv, L, splits);
+        std::vector<int> lens = attn_lengths(who, lengths, B, L);
+        float sc = 1.0f / std::sqrt(static_cast<float>(payload::kAttnD));
+        if (!scale.is_none()) {
+          sc = scale.cast<float>();
+          if (!std::isfinite(sc)) throw py::value_error("attn_decode: scale not finite");
+        }
+        const float* pq = q.data();
+        const float* pk = k.data();
+        const float* pv = v.data();
+        for (py::ssize_t i = 0, n = q.size(); i < n; ++i)
+          if (!std::isfinite(pq[i]))
+            throw py::value_error("attn_decode: q has a non-finite element");
+        for (py::ssize_t i = 0, n = k.size(); i < n; ++i)
+          if (!std::isfinite(pk[i]) || !std::isfinite(pv[i]))
+            throw py::value_error("attn_decode: k or v has a non-finite element");
+        py::array_t<float> o({B, Hq, static_cast<py::ssize_t>(payload::kAttnD)});
+        float* po = o.mutable_data();
+        {
+          py::gil_scoped_release rel;
+          payload::attn_decode(pq, pk, pv, lens.empty() ? nullptr : lens.data(), po,
+                               static_cast<int>(B), static_cast<int>(Hq),
+                               static_cast<int>(Hkv), static_cast<int>(L), sc, splits,
+                               device);
+        }
+        return o;
+      },
+      py::arg("q"), py::arg("k"), py::arg("v"), py::arg("lengths") = py::none(),
+      py::arg("scale") = py::none(), py::arg("splits") = 0, py::arg("device") = 0,
+      "o (B,Hq,128) float32 = softmax(scale q.k) v over the first lengths[b] keys: "
+      "single-token grouped-query attention over a KV cache, q (B,Hq,128), k and "
+      "v (B,Hkv,L,128) rounded to bf16, on the MFMA split-KV kernel; scale=None "
+      "is 1/sqrt(128), splits=0 is auto; ValueError on an unsupported shape, "
+      "length, split count or a non-finite input");
+
+  m.def(
+      "attn_check_pattern",
+      [attn_lengths, attn_shape](int batch, int hq, int hkv, int length,
+                                 py::object lengths) {
+        attn_shape("attn_check_pattern", batch, hq, hkv, length, 0);
+        std::vector<int> lens = attn_lengths("attn_check_pattern", lengths, batch, length);
+        const py::ssize_t D = payload::kAttnD;
+        py::array_t<float> q({static_cast<py::ssize_t>(batch), static_cast<py::ssize_t>(hq), D});
+        py::array_t<float> e({static_cast<py::ssize_t>(batch), static_cast<py::ssize_t>(hq), D});
+        py::array_t<float> k({static_cast<py::ssize_t>(batch), static_cast<py::ssize_t>(hkv),
+                              static_cast<py::ssize_t>(length), D});
+        py::array_t<float> v({static_cast<py::ssize_t>(batch), static_cast<py::ssize_t>(hkv),
+                              static_cast<py::ssize_t>(length), D});
+        payload::attn_check_pattern(q.mutable_data(), k.mutable_data(),
+                                    v.mutable_data(), e.mutable_data(), batch, hq, hkv,
+                                    length, lens.empty() ? nullptr : lens.data());
+        return py::make_tuple(q, k, v, e);
+      },
+      py::arg("batch"), py::arg("hq"), py::arg("hkv"), py::arg("length"),
+      py::arg("lengths") = py::none(),
+      "(q, k, v, expected) of the exact selection pattern: small integers, K zero "
+      "at min(32, largest power of two <= len) selected keys per (sequence, kv "
+      "head) and <= -16 elsewhere, expected = mean of v over the selected keys; "
+      "host only, no GPU");
+
+  m.def(
+      "run_attn_check",
+      [attn_shape](int batch, int hq, int hkv, int length, int splits, int device) {
+        attn_shape("run_attn_check", batch, hq, hkv, length, splits);
+        payload::AttnCheck r;
+        {
+          py::gil_scoped_release rel;
+          r = payload::run_attn_check(batch, hq, hkv, length, splits, device);
+        }
+        py::dict d;
+        d["max_err"] = r.max_err;
+        d["max_rel"] = r.max_rel;
+        return d;
+      },
+      py::arg("batch"), py::arg("hq"), py::arg("hkv"), py::arg("length"),
+      py::arg("splits") = 0, py::arg("device") = 0,
+      "decode attention self-check at full lengths: max_err of the selection "
+      "pattern (expect exactly 0) and max_rel = max |o - fp64 ref| / max |v| of a "
+      "dense pattern (expect <= 2^-8)");
+
+  m.def(
+      "run_attn",
+      [attn_shape](int batch, int hq, int hkv, int length, int iters, int device) {
+        attn_shape("run_attn", batch, hq, hkv, length, 0);
+        if (iters < 1) throw py::value_error("run_attn: iters must be >= 1");
+        payload::AttnResult r;
+        {
+          py::gil_scoped_release rel;
+          r = payload::run_attn(batch, hq, hkv, length, iters, device);
+        }
+        py::dict d;
+        d["batch"] = batch;
+        d["hq"] = hq;
+        d["hkv"] = hkv;
+        d["len"] = length;
+        d["iters"] = iters;
+        d["kv_gb_per_s"] = r.kv_gb_s;
+        d["steps_per_s"] = r.steps_per_s;
+        d["tok_per_s"] = r.tok_per_s;
+        d["max_err"] = r.max_err;
+        return d;
+      },
+      py::arg("batch") = 32, py::arg("hq") = 64, py::arg("hkv") = 8,
+      py::arg("length") = 4096, py::arg("iters") = 10, py::arg("device") = 0,
+      "timed decode attention on the selection pattern (device-filled cache, "
+      "512 MiB of K and V at the default shape), 16 output rows checked exactly");
 }

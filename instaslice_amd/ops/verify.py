@@ -35,6 +35,15 @@ fails "mxgemm" unless the maximum error is exactly zero. It exercises a
 different instruction and datapath than the bf16 GEMM that `verify` runs, so a
 partition can pass one and fail the other. Its TFLOP/s is carried in the
 report and never judged.
+
+So has the serving path. `run_attn` runs `instaslice-payload attn` (KV-cache
+decode attention: single-token grouped-query attention at head dim 128, K and
+V streamed through the bf16 MFMA with an fp32 online softmax and a split-KV
+merge; a self-check, then a timed run over 512 MiB of K and V) and
+`judge_attn` fails "attn" unless the exact pattern's maximum error is zero and
+the dense pattern's error relative to max |v| is within 2**-8, the bound that
+rounding the softmax weights to bf16 allows twice over. KV bytes/s, decode
+steps/s and tokens/s are carried in the report and never judged.
 """
 
 from __future__ import annotations
@@ -42,6 +51,7 @@ from __future__ import annotations
 import json
 import os
 import subprocess
+import math
 from typing import Callable, Dict, Optional
 
 from instaslice_amd.partition.profiles import parse_profile_name
@@ -286,6 +296,80 @@ def run_mxgemm(profile_name: str, env: Optional[Dict[str, str]] = None,
                         f"mxgemm failed (exit {proc.returncode}): "
                         f"{report.get('error', 'no report fields')}", report)
     verdict = judge_mxgemm(report, profile_name)
+    if proc.returncode != 0:
+        # clean-looking fields do not outvote a non-zero exit
+        verdict["ok"] = False
+        verdict["reason"] = f"payload exited {proc.returncode}"
+    return verdict
+
+
+# ---- attn -------------------------------------------------------------------
+
+# max |o - fp64 reference| / max |v| of the dense pattern: each weight rounded
+# to bf16 is off by at most 2**-9 relative while the normaliser is summed from
+# the unrounded weights, so the output is off by at most 2**-9 max |v| plus
+# fp32 terms of order 1e-6; the bound doubles that
+ATTN_MAX_REL = 2.0 ** -8
+
+
+def _is_real(value) -> bool:
+    return isinstance(value, (int, float)) and not isinstance(value, bool) \
+        and math.isfinite(value)
+
+
+def judge_attn(report: dict, profile_name: str) -> dict:
+    """Judge an `instaslice-payload attn` report: "attn" fails unless
+    `max_err` is a numeric zero, `max_rel` is a real number in [0, 2**-8] and
+    `batch`, `hq`, `hkv`, `len`, `iters` are integer counts >= 1.
+    `kv_gb_per_s`, `steps_per_s` and `tok_per_s` are carried and never judged.
+    Pure; the report's own `ok` is not trusted. ValueError on a profile name
+    that does not parse."""
+    parse_profile_name(profile_name)
+    clean = (_is_zero(report.get("max_err"))
+             and _is_real(report.get("max_rel"))
+             and 0 <= report["max_rel"] <= ATTN_MAX_REL
+             and all(_is_count(report.get(key)) and report[key] >= 1
+                     for key in ("batch", "hq", "hkv", "len", "iters")))
+    failed = [] if clean else ["attn"]
+    return {"ok": not failed, "failed": failed, "profile": profile_name,
+            "report": report}
+
+
+def run_attn(profile_name: str, env: Optional[Dict[str, str]] = None,
+             runner: Callable = subprocess.run) -> dict:
+    """Run `instaslice-payload attn` (default shape and iterations) in a fresh
+    child with `env` and judge its report, with the same contract as
+    `run_mxgemm`: every way the child can fail comes back as `ok: False` with
+    a `reason`, and only an unparseable profile name raises (ValueError)."""
+    parse_profile_name(profile_name)
+    child_env = dict(os.environ)
+    child_env.update({k: str(v) for k, v in (env or {}).items()})
+    try:
+        proc = runner([BIN_PATH, "attn"], capture_output=True, text=True,
+                      timeout=CHILD_TIMEOUT_S, env=child_env)
+    except FileNotFoundError:
+        return _not_run(profile_name, f"payload binary not found: {BIN_PATH}")
+    except subprocess.TimeoutExpired:
+        return _not_run(profile_name,
+                        f"attn timed out after {CHILD_TIMEOUT_S:.0f} s")
+    except OSError as e:
+        return _not_run(profile_name, f"could not start payload binary: {e}")
+
+    lines = [ln for ln in (proc.stdout or "").splitlines() if ln.strip()]
+    try:
+        report = json.loads(lines[-1]) if lines else None
+    except ValueError:
+        report = None
+    if not isinstance(report, dict):
+        tail = (proc.stdout or "").strip()[-200:]
+        return _not_run(profile_name,
+                        f"non-JSON output (exit {proc.returncode}): {tail!r}")
+    if "max_err" not in report:
+        # the binary's catch-all error line: {"ok": false, "error": "..."}
+        return _not_run(profile_name,
+                        f"attn failed (exit {proc.returncode}): "
+                        f"{report.get('error', 'no report fields')}", report)
+    verdict = judge_attn(report, profile_name)
     if proc.returncode != 0:
         # clean-looking fields do not outvote a non-zero exit
         verdict["ok"] = False
