@@ -19,13 +19,15 @@
     python -m instaslice_amd top        --store HOST:PORT [--interval S]
     python -m instaslice_amd cordon     --store HOST:PORT --node N [--uncordon]
     python -m instaslice_amd payload    [info|vecadd|membw|busy|census|gemm|
-                                         mxgemm|attn|memcheck|verify] ...
+                                         mxgemm|mx4gemm|attn|memcheck|verify] ...
     python -m instaslice_amd verify     --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
     python -m instaslice_amd memcheck   --profile NAME [--gb G | --fraction F]
                                         [--passes N]
                                         [--visible-devices UUID_OR_INDEX]
     python -m instaslice_amd mxgemm     --profile NAME
+                                        [--visible-devices UUID_OR_INDEX]
+    python -m instaslice_amd mx4gemm    --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
     python -m instaslice_amd attn       --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
@@ -425,6 +427,24 @@ def cmd_mxgemm(args) -> int:
     return 0 if verdict["ok"] else 1
 
 
+def cmd_mx4gemm(args) -> int:
+    """Run the MXFP4 block-scaled GEMM payload inside the visible partition
+    and judge it against the requested profile; prints the judged JSON, exit
+    0 iff ok."""
+    from instaslice_amd.ops import verify
+
+    env = {}
+    if args.visible_devices is not None:
+        env["ROCR_VISIBLE_DEVICES"] = args.visible_devices
+    try:
+        verdict = verify.run_mx4gemm(args.profile, env=env)
+    except ValueError as e:
+        verdict = {"ok": False, "failed": [], "profile": args.profile,
+                   "reason": str(e), "report": None}
+    print(json.dumps(verdict))
+    return 0 if verdict["ok"] else 1
+
+
 def cmd_attn(args) -> int:
     """Run the KV-cache decode attention payload inside the visible partition
     and judge it against the requested profile; prints the judged JSON, exit
@@ -574,6 +594,16 @@ def main(argv=None) -> int:
                    help="ROCR_VISIBLE_DEVICES for the probe (partition UUID "
                         "or index); default: inherit the environment")
     p.set_defaults(fn=cmd_mxgemm)
+
+    p = sub.add_parser("mx4gemm",
+                       help="exact-check and time the MXFP4 block-scaled "
+                            "matrix path of the visible partition, judge it "
+                            "against a profile")
+    p.add_argument("--profile", required=True, help="e.g. cpx-1x36")
+    p.add_argument("--visible-devices", default=None,
+                   help="ROCR_VISIBLE_DEVICES for the probe (partition UUID "
+                        "or index); default: inherit the environment")
+    p.set_defaults(fn=cmd_mx4gemm)
 
     p = sub.add_parser("attn",
                        help="check and time KV-cache decode attention (the "

@@ -20,7 +20,12 @@
 //                per 32 elements), exact-checked and timed: the low-precision
 //                matrix path, a different instruction and datapath than bf16
 //                (payload_mxgemm.hpp, included below)
-//   memcheck     moving-inversions memory test with an address-derived
+//   mx4gemm      MXFP4 block-scaled MFMA GEMM (OCP e2m1 operands, two to a
+//                byte, E8M0 scales per 32 elements), exact-checked and timed:
+//                the 4-bit matrix path, the same instruction with other format
+//                selectors and half the operand registers
+//                (payload_mxfp4.hpp, included below)
+//   memcheck    moving-inversions memory test with an address-derived
 //                pattern at streaming rate: the HBM a profile promises is
 //                there, holds data and does not alias (payload_memcheck.hpp,
 //                included below)
@@ -283,6 +288,10 @@ inline int device_count() {
 
 // MXFP8 block-scaled MFMA GEMM payload: same helpers, plus the gemm pattern
 #include "payload_mxgemm.hpp"
+
+// MXFP4 block-scaled MFMA GEMM payload: the MXFP8 one's LDS and scale images,
+// pattern and limits
+#include "payload_mxfp4.hpp"
 
 // memcheck payload: also uses grid_for, detail::DeviceBuffer and detail::Event
 #include "payload_memcheck.hpp"

@@ -20,6 +20,13 @@
 //                                             timed (default 4096 4096 2048,
 //                                             10 iters; K <= 2048);
 //                                             exit 1 unless max_err == 0
+//   instaslice-payload mx4gemm [M N K [ITERS]] MXFP4 block-scaled MFMA GEMM
+//                                             (e2m1 operands, two to a byte,
+//                                             E8M0 scales per 32 elements),
+//                                             exact-checked and timed on the
+//                                             mxgemm pattern (default 4096
+//                                             4096 2048, 10 iters; K <= 2048);
+//                                             exit 1 unless max_err == 0
 //   instaslice-payload memcheck [BYTES [PASSES [FLIP_OFFSET FLIP_MASK]]]
 //                                             moving-inversions memory test
 //                                             of one BYTES buffer (default
@@ -162,6 +169,18 @@ int main(int argc, char** argv) {
           "\"iters\": %d, \"tflops\": %.2f, \"max_err\": %g}\n",
           ok ? "true" : "false", m, n, k, iters, r.tflops, json_num(r.max_err));
       return ok ? 0 : 1;
+    } else if (std::strcmp(cmd, "mx4gemm") == 0) {
+      int m = argc > 4 ? std::atoi(argv[2]) : 4096;
+      int n = argc > 4 ? std::atoi(argv[3]) : 4096;
+      int k = argc > 4 ? std::atoi(argv[4]) : 2048;
+      int iters = argc > 5 ? std::atoi(argv[5]) : 10;
+      GemmResult r = run_mx4gemm(m, n, k, iters);
+      bool ok = r.max_err == 0.0;
+      std::printf(
+          "{\"ok\": %s, \"cmd\": \"mx4gemm\", \"m\": %d, \"n\": %d, \"k\": %d, "
+          "\"iters\": %d, \"tflops\": %.2f, \"max_err\": %g}\n",
+          ok ? "true" : "false", m, n, k, iters, r.tflops, json_num(r.max_err));
+      return ok ? 0 : 1;
     } else if (std::strcmp(cmd, "attn") == 0) {
       int b = argc > 5 ? std::atoi(argv[2]) : 32;
       int hq = argc > 5 ? std::atoi(argv[3]) : 64;
@@ -224,7 +243,7 @@ int main(int argc, char** argv) {
     } else if (std::strcmp(cmd, "serve") == 0) {
       // warm-pool worker: one line per request, one JSON line per reply
       //   vecadd <n> | busy <ms> | gemm [M N K] | mxgemm [M N K] |
-      //   attn [B HQ HKV L] | memcheck [BYTES] | ping | quit
+      //   mx4gemm [M N K] | attn [B HQ HKV L] | memcheck [BYTES] | ping | quit
       std::string line;
       while (std::getline(std::cin, line)) {
         std::istringstream iss(line);
@@ -256,6 +275,14 @@ int main(int argc, char** argv) {
             double err = run_mxgemm_check(m, n, k);
             std::printf(
                 "{\"ok\": %s, \"cmd\": \"mxgemm\", \"m\": %d, \"n\": %d, "
+                "\"k\": %d, \"max_err\": %g}\n",
+                err == 0.0 ? "true" : "false", m, n, k, json_num(err));
+          } else if (verb == "mx4gemm") {
+            int m = 96, n = 160, k = 224, tm, tn, tk;
+            if (iss >> tm >> tn >> tk) { m = tm; n = tn; k = tk; }
+            double err = run_mx4gemm_check(m, n, k);
+            std::printf(
+                "{\"ok\": %s, \"cmd\": \"mx4gemm\", \"m\": %d, \"n\": %d, "
                 "\"k\": %d, \"max_err\": %g}\n",
                 err == 0.0 ? "true" : "false", m, n, k, json_num(err));
           } else if (verb == "attn") {

@@ -14,7 +14,7 @@ namespace py = pybind11;
 
 PYBIND11_MODULE(_payload, m) {
   m.doc() = "gfx950 HIP payload kernels (vecadd / membw / busy / xcd census / gemm / "
-            "mxgemm / memcheck / attn)";
+            "mxgemm / mx4gemm / memcheck / attn)";
 
   m.def("device_count", &payload::device_count,
         "Number of visible HIP devices (0 if no GPU/driver)");
@@ -300,6 +300,188 @@ PYBIND11_MODULE(_payload, m) {
       py::arg("m") = 4096, py::arg("n") = 4096, py::arg("k") = 2048,
       py::arg("iters") = 10, py::arg("device") = 0,
       "timed MXFP8 block-scaled MFMA GEMM, 256 outputs spot-checked exactly; "
+      "K <= 2048");
+
+  // ---- MXFP4 ---------------------------------------------------------------
+
+  auto no_nan = [](const char* who, const f32_array& x) {
+    const float* src = x.data();
+    for (py::ssize_t i = 0, n = x.size(); i < n; ++i)
+      if (std::isnan(src[i]))
+        throw py::value_error(std::string(who) + ": x has a NaN element (e2m1 has no NaN)");
+  };
+  auto e2m1_codes = [](const char* who, const u8_array& codes) {
+    const uint8_t* src = codes.data();
+    for (py::ssize_t i = 0, n = codes.size(); i < n; ++i)
+      if (src[i] > 15)
+        throw py::value_error(std::string(who) + ": an e2m1 code must be in 0 .. 15");
+  };
+
+  m.def(
+      "to_e2m1",
+      [no_nan](f32_array x) {
+        no_nan("to_e2m1", x);
+        py::array_t<uint8_t> out(
+            std::vector<py::ssize_t>(x.shape(), x.shape() + x.ndim()));
+        const float* src = x.data();
+        uint8_t* dst = out.mutable_data();
+        for (py::ssize_t i = 0, n = x.size(); i < n; ++i)
+          dst[i] = payload::to_e2m1_sat(src[i]);
+        return out;
+      },
+      py::arg("x"),
+      "float32 -> OCP e2m1 code (uint8, 0..15, bit 3 the sign), nearest value "
+      "with ties to the even code, saturating at +-6; ValueError on NaN; host "
+      "only, no GPU");
+
+  m.def(
+      "from_e2m1",
+      [e2m1_codes](u8_array codes) {
+        e2m1_codes("from_e2m1", codes);
+        py::array_t<float> out(
+            std::vector<py::ssize_t>(codes.shape(), codes.shape() + codes.ndim()));
+        const uint8_t* src = codes.data();
+        float* dst = out.mutable_data();
+        for (py::ssize_t i = 0, n = codes.size(); i < n; ++i)
+          dst[i] = payload::from_e2m1(src[i]);
+        return out;
+      },
+      py::arg("codes"),
+      "OCP e2m1 code (uint8, 0..15) -> float32; ValueError on a code above 15; "
+      "host only, no GPU");
+
+  m.def(
+      "mx4_quantize",
+      [no_nan](f32_array x) {
+        if (x.ndim() < 1)
+          throw py::value_error("mx4_quantize: x must have at least one axis");
+        if (x.shape(x.ndim() - 1) < 1 || x.shape(x.ndim() - 1) > INT32_MAX)
+          throw py::value_error("mx4_quantize: bad length of the last axis");
+        no_nan("mx4_quantize", x);
+        const int K = static_cast<int>(x.shape(x.ndim() - 1));
+        const py::ssize_t blocks = (K + payload::kMxBlock - 1) / payload::kMxBlock;
+        std::vector<py::ssize_t> shape(x.shape(), x.shape() + x.ndim());
+        py::array_t<uint8_t> codes(shape);
+        shape.back() = blocks;
+        py::array_t<uint8_t> scales(shape);
+        const float* src = x.data();
+        uint8_t* pc = codes.mutable_data();
+        uint8_t* ps = scales.mutable_data();
+        for (py::ssize_t r = 0, rows = x.size() / K; r < rows; ++r)
+          payload::mx4_quantize_row(src + r * K, K, pc + r * K, ps + r * blocks);
+        return py::make_tuple(codes, scales);
+      },
+      py::arg("x"),
+      "OCP MX quantization to e2m1 along the last axis: (codes uint8 [..., K], one "
+      "code 0..15 per byte, scales uint8 [..., ceil(K/32)]); ValueError on NaN; "
+      "host only, no GPU");
+
+  m.def(
+      "pack_fp4",
+      [e2m1_codes](u8_array codes) {
+        if (codes.ndim() < 1)
+          throw py::value_error("pack_fp4: codes must have at least one axis");
+        if (codes.shape(codes.ndim() - 1) < 1 ||
+            codes.shape(codes.ndim() - 1) > INT32_MAX)
+          throw py::value_error("pack_fp4: bad length of the last axis");
+        e2m1_codes("pack_fp4", codes);
+        const int K = static_cast<int>(codes.shape(codes.ndim() - 1));
+        const py::ssize_t bytes = (K + 1) / 2;
+        std::vector<py::ssize_t> shape(codes.shape(), codes.shape() + codes.ndim());
+        shape.back() = bytes;
+        py::array_t<uint8_t> out(shape);
+        const uint8_t* src = codes.data();
+        uint8_t* dst = out.mutable_data();
+        for (py::ssize_t r = 0, rows = codes.size() / K; r < rows; ++r)
+          payload::pack_fp4(src + r * K, K, dst + r * bytes);
+        return out;
+      },
+      py::arg("codes"),
+      "the device byte image of e2m1 codes along the last axis: uint8 [..., "
+      "ceil(K/2)], even k in bits 3:0 and odd k in bits 7:4, an odd tail padded "
+      "with code 0; ValueError on a code above 15; host only, no GPU");
+
+  m.def(
+      "gemm_mxfp4",
+      [mx_dims](f32_array a, f32_array b, int device) {
+        auto [M, N, K] = mx_dims("gemm_mxfp4", a, b);
+        py::array_t<float> c({static_cast<py::ssize_t>(M), static_cast<py::ssize_t>(N)});
+        const float* pa = a.data();
+        const float* pb = b.data();
+        float* pc = c.mutable_data();
+        {
+          py::gil_scoped_release rel;
+          payload::gemm_mxfp4(pa, pb, pc, M, N, K, device);
+        }
+        return c;
+      },
+      py::arg("a"), py::arg("b"), py::arg("device") = 0,
+      "C (M,N) float32 = mx4(a (M,K)) @ mx4(b (K,N)): rows of a and columns of b "
+      "MX-quantized to e2m1 with E8M0 block scales, on the block-scaled MFMA "
+      "kernel; ValueError on a non-finite input");
+
+  m.def(
+      "gemm_mxfp4_raw",
+      [mx_dims, e2m1_codes](u8_array a_codes, u8_array a_scales, u8_array b_codes,
+                            u8_array b_scales, int device) {
+        auto [M, N, K] = mx_dims("gemm_mxfp4_raw", a_codes, b_codes);
+        const py::ssize_t blocks = (K + payload::kMxBlock - 1) / payload::kMxBlock;
+        if (a_scales.ndim() != 2 || a_scales.shape(0) != M ||
+            a_scales.shape(1) != blocks)
+          throw py::value_error("gemm_mxfp4_raw: a_scales must be (M, ceil(K/32))");
+        if (b_scales.ndim() != 2 || b_scales.shape(0) != blocks ||
+            b_scales.shape(1) != N)
+          throw py::value_error("gemm_mxfp4_raw: b_scales must be (ceil(K/32), N)");
+        e2m1_codes("gemm_mxfp4_raw", a_codes);
+        e2m1_codes("gemm_mxfp4_raw", b_codes);
+        py::array_t<float> c({static_cast<py::ssize_t>(M), static_cast<py::ssize_t>(N)});
+        const uint8_t* pa = a_codes.data();
+        const uint8_t* psa = a_scales.data();
+        const uint8_t* pb = b_codes.data();
+        const uint8_t* psb = b_scales.data();
+        float* pc = c.mutable_data();
+        {
+          py::gil_scoped_release rel;
+          payload::gemm_mxfp4_raw(pa, psa, pb, psb, pc, M, N, K, device);
+        }
+        return c;
+      },
+      py::arg("a_codes"), py::arg("a_scales"), py::arg("b_codes"),
+      py::arg("b_scales"), py::arg("device") = 0,
+      "C (M,N) float32 from already quantized operands: e2m1 codes (M,K) and "
+      "(K,N), one code 0..15 per byte, E8M0 scales (M,ceil(K/32)) and "
+      "(ceil(K/32),N), all uint8; ValueError on a code above 15");
+
+  m.def(
+      "run_mx4gemm_check",
+      [](int mm, int n, int k, int device) {
+        py::gil_scoped_release rel;
+        return payload::run_mx4gemm_check(mm, n, k, device);
+      },
+      py::arg("m"), py::arg("n"), py::arg("k"), py::arg("device") = 0,
+      "scaled integer-pattern MXFP4 GEMM vs host int64 reference; returns max "
+      "abs error (expect 0); K <= 2048");
+
+  m.def(
+      "run_mx4gemm",
+      [](int mm, int n, int k, int iters, int device) {
+        payload::GemmResult r;
+        {
+          py::gil_scoped_release rel;
+          r = payload::run_mx4gemm(mm, n, k, iters, device);
+        }
+        py::dict d;
+        d["m"] = mm;
+        d["n"] = n;
+        d["k"] = k;
+        d["iters"] = iters;
+        d["tflops"] = r.tflops;
+        d["max_err"] = r.max_err;
+        return d;
+      },
+      py::arg("m") = 4096, py::arg("n") = 4096, py::arg("k") = 2048,
+      py::arg("iters") = 10, py::arg("device") = 0,
+      "timed MXFP4 block-scaled MFMA GEMM, 256 outputs spot-checked exactly; "
       "K <= 2048");
 
   m.def(

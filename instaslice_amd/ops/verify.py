@@ -36,6 +36,15 @@ different instruction and datapath than the bf16 GEMM that `verify` runs, so a
 partition can pass one and fail the other. Its TFLOP/s is carried in the
 report and never judged.
 
+The 4-bit matrix path has one as well. `run_mx4gemm` runs `instaslice-payload
+mx4gemm` (the MXFP4 block-scaled MFMA GEMM: e2m1 operands packed two to a
+byte, E8M0 scales, the same pattern, shape and checks as `mxgemm`) and
+`judge_mx4gemm` fails "mx4gemm" unless the maximum error is exactly zero. It is
+the same instruction with other format selectors and half the operand
+registers, at twice the MXFP8 rate per clock, so a partition can pass `mxgemm`
+and still be wrong or slow here. Its TFLOP/s is carried in the report and
+never judged.
+
 So has the serving path. `run_attn` runs `instaslice-payload attn` (KV-cache
 decode attention: single-token grouped-query attention at head dim 128, K and
 V streamed through the bf16 MFMA with an fp32 online softmax and a split-KV
@@ -296,6 +305,65 @@ def run_mxgemm(profile_name: str, env: Optional[Dict[str, str]] = None,
                         f"mxgemm failed (exit {proc.returncode}): "
                         f"{report.get('error', 'no report fields')}", report)
     verdict = judge_mxgemm(report, profile_name)
+    if proc.returncode != 0:
+        # clean-looking fields do not outvote a non-zero exit
+        verdict["ok"] = False
+        verdict["reason"] = f"payload exited {proc.returncode}"
+    return verdict
+
+
+# ---- mx4gemm ----------------------------------------------------------------
+
+def judge_mx4gemm(report: dict, profile_name: str) -> dict:
+    """Judge an `instaslice-payload mx4gemm` report: "mx4gemm" fails unless
+    `max_err` is a numeric zero and `m`, `n`, `k`, `iters` are integer counts
+    >= 1. `tflops` is carried and never judged. Pure; the report's own `ok`
+    is not trusted. ValueError on a profile name that does not parse."""
+    parse_profile_name(profile_name)
+    clean = (_is_zero(report.get("max_err"))
+             and all(_is_count(report.get(key)) and report[key] >= 1
+                     for key in ("m", "n", "k", "iters")))
+    failed = [] if clean else ["mx4gemm"]
+    return {"ok": not failed, "failed": failed, "profile": profile_name,
+            "report": report}
+
+
+def run_mx4gemm(profile_name: str, env: Optional[Dict[str, str]] = None,
+                runner: Callable = subprocess.run) -> dict:
+    """Run `instaslice-payload mx4gemm` (default shape and iterations) in a
+    fresh child with `env` and judge its report, with the same contract as
+    `run_mxgemm`: every way the child can fail comes back as `ok: False`
+    with a `reason`, and only an unparseable profile name raises
+    (ValueError)."""
+    parse_profile_name(profile_name)
+    child_env = dict(os.environ)
+    child_env.update({k: str(v) for k, v in (env or {}).items()})
+    try:
+        proc = runner([BIN_PATH, "mx4gemm"], capture_output=True, text=True,
+                      timeout=CHILD_TIMEOUT_S, env=child_env)
+    except FileNotFoundError:
+        return _not_run(profile_name, f"payload binary not found: {BIN_PATH}")
+    except subprocess.TimeoutExpired:
+        return _not_run(profile_name,
+                        f"mx4gemm timed out after {CHILD_TIMEOUT_S:.0f} s")
+    except OSError as e:
+        return _not_run(profile_name, f"could not start payload binary: {e}")
+
+    lines = [ln for ln in (proc.stdout or "").splitlines() if ln.strip()]
+    try:
+        report = json.loads(lines[-1]) if lines else None
+    except ValueError:
+        report = None
+    if not isinstance(report, dict):
+        tail = (proc.stdout or "").strip()[-200:]
+        return _not_run(profile_name,
+                        f"non-JSON output (exit {proc.returncode}): {tail!r}")
+    if "max_err" not in report:
+        # the binary's catch-all error line: {"ok": false, "error": "..."}
+        return _not_run(profile_name,
+                        f"mx4gemm failed (exit {proc.returncode}): "
+                        f"{report.get('error', 'no report fields')}", report)
+    verdict = judge_mx4gemm(report, profile_name)
     if proc.returncode != 0:
         # clean-looking fields do not outvote a non-zero exit
         verdict["ok"] = False
