@@ -100,7 +100,9 @@ def build(force: bool = False) -> None:
     hdr_mxgemm = ops_dir / "csrc" / "payload_mxgemm.hpp"  # likewise
     hdr_mxfp4 = ops_dir / "csrc" / "payload_mxfp4.hpp"  # likewise
     hdr_attn = ops_dir / "csrc" / "payload_attn.hpp"  # likewise
-    payload_hdrs = [hdr, hdr_gemm, hdr_memcheck, hdr_mxgemm, hdr_mxfp4, hdr_attn]
+    hdr_prefill = ops_dir / "csrc" / "payload_prefill.hpp"  # likewise
+    payload_hdrs = [hdr, hdr_gemm, hdr_memcheck, hdr_mxgemm, hdr_mxfp4, hdr_attn,
+                    hdr_prefill]
     out = ops_dir / f"_payload{EXT}"
     if force or not newer(out, [src, *payload_hdrs], ARCH):
         run([HIPCC, f"--offload-arch={ARCH}", "-shared", *common,

@@ -19,7 +19,8 @@
     python -m instaslice_amd top        --store HOST:PORT [--interval S]
     python -m instaslice_amd cordon     --store HOST:PORT --node N [--uncordon]
     python -m instaslice_amd payload    [info|vecadd|membw|busy|census|gemm|
-                                         mxgemm|mx4gemm|attn|memcheck|verify] ...
+                                         mxgemm|mx4gemm|attn|prefill|memcheck|
+                                         verify] ...
     python -m instaslice_amd verify     --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
     python -m instaslice_amd memcheck   --profile NAME [--gb G | --fraction F]
@@ -30,6 +31,8 @@
     python -m instaslice_amd mx4gemm    --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
     python -m instaslice_amd attn       --profile NAME
+                                        [--visible-devices UUID_OR_INDEX]
+    python -m instaslice_amd prefill    --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
 
 NODE_NAME env is honored for the daemonset (downward-API parity with
@@ -463,6 +466,24 @@ def cmd_attn(args) -> int:
     return 0 if verdict["ok"] else 1
 
 
+def cmd_prefill(args) -> int:
+    """Run the causal prefill attention payload inside the visible partition
+    and judge it against the requested profile; prints the judged JSON, exit
+    0 iff ok."""
+    from instaslice_amd.ops import verify
+
+    env = {}
+    if args.visible_devices is not None:
+        env["ROCR_VISIBLE_DEVICES"] = args.visible_devices
+    try:
+        verdict = verify.run_prefill(args.profile, env=env)
+    except ValueError as e:
+        verdict = {"ok": False, "failed": [], "profile": args.profile,
+                   "reason": str(e), "report": None}
+    print(json.dumps(verdict))
+    return 0 if verdict["ok"] else 1
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="instaslice-amd")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -614,6 +635,16 @@ def main(argv=None) -> int:
                    help="ROCR_VISIBLE_DEVICES for the probe (partition UUID "
                         "or index); default: inherit the environment")
     p.set_defaults(fn=cmd_attn)
+
+    p = sub.add_parser("prefill",
+                       help="check and time causal prefill attention (the "
+                            "compute-bound half of serving) in the visible "
+                            "partition, judge it against a profile")
+    p.add_argument("--profile", required=True, help="e.g. cpx-1x36")
+    p.add_argument("--visible-devices", default=None,
+                   help="ROCR_VISIBLE_DEVICES for the probe (partition UUID "
+                        "or index); default: inherit the environment")
+    p.set_defaults(fn=cmd_prefill)
 
     args = ap.parse_args(argv)
     return args.fn(args)

@@ -34,6 +34,13 @@
 //                straight through the bf16 MFMA with an fp32 online softmax,
 //                exact-checked, bound-checked and timed: the hot kernel of an
 //                LLM server in decode (payload_attn.hpp, included below)
+//   prefill      causal prefill attention over a whole prompt (grouped-query,
+//                head dim 128): K and V tiles staged through swizzled,
+//                double-buffered LDS and shared by the workgroup's waves, both
+//                products on the bf16 MFMA with the fp32 online softmax in
+//                between, exact-checked, bound-checked and timed: the
+//                compute-bound half of serving (payload_prefill.hpp, included
+//                below)
 //
 // Kernel style per the CDNA4 playbook: 256-thread blocks (4 waves of 64),
 // float4 (dwordx4) streaming accesses for coalescing, grid-strided loops
@@ -298,3 +305,6 @@ inline int device_count() {
 
 // decode attention payload: bf16x8, f32x4, to_bf16_rne and the detail helpers
 #include "payload_attn.hpp"
+
+// prefill attention payload: the decode one's head dim, patterns and scale
+#include "payload_prefill.hpp"

@@ -51,6 +51,23 @@
 //                                             the KV split count of the timed
 //                                             run; exit 1 unless max_err == 0
 //                                             and max_rel <= 2^-8
+//   instaslice-payload prefill [B HQ HKV L [ITERS [CAUSAL [PATTERN]]]]
+//                                             causal prefill attention (bf16
+//                                             MFMA, K and V tiles through LDS,
+//                                             fp32 online softmax; head dim
+//                                             128): the self-check at 2 8 2 300
+//                                             (exact pattern and a dense
+//                                             pattern against fp64), then a
+//                                             timed run on the dense pattern
+//                                             (default 8 64 8 4096, 10 iters,
+//                                             CAUSAL 1) with 16 rows checked
+//                                             against fp64; TFLOP/s counts the
+//                                             unmasked pairs only; PATTERN 1
+//                                             times the selection pattern
+//                                             instead (low-entropy data: a
+//                                             flattering rate, for comparison
+//                                             only); exit 1 unless max_err ==
+//                                             0 and max_rel <= 2^-8
 //   instaslice-payload verify [XCDS]          census + vecadd + gemm check +
 //                                             membw + timed gemm in one JSON
 //                                             line; XCDS (0 or absent: not
@@ -200,6 +217,27 @@ int main(int argc, char** argv) {
           ok ? "true" : "false", b, hq, hkv, len, iters, r.kv_gb_s, r.steps_per_s,
           r.tok_per_s, json_num(max_err), json_num(c.max_rel));
       return ok ? 0 : 1;
+    } else if (std::strcmp(cmd, "prefill") == 0) {
+      int b = argc > 5 ? std::atoi(argv[2]) : 8;
+      int hq = argc > 5 ? std::atoi(argv[3]) : 64;
+      int hkv = argc > 5 ? std::atoi(argv[4]) : 8;
+      int len = argc > 5 ? std::atoi(argv[5]) : 4096;
+      int iters = argc > 6 ? std::atoi(argv[6]) : 10;
+      bool causal = argc > 7 ? std::atoi(argv[7]) != 0 : true;
+      int pattern = argc > 8 ? std::atoi(argv[8]) : kPrefillDense;
+      PrefillCheck c = run_prefill_check(2, 8, 2, 300, causal);
+      PrefillResult r = run_prefill(b, hq, hkv, len, iters, causal, 0, pattern);
+      double max_rel = r.max_rel > c.max_rel ? r.max_rel : c.max_rel;
+      if (std::isnan(r.max_rel) || std::isnan(c.max_rel)) max_rel = INFINITY;
+      bool ok = c.max_err == 0.0 && max_rel <= kPrefillRelBound;
+      std::printf(
+          "{\"ok\": %s, \"cmd\": \"prefill\", \"batch\": %d, \"hq\": %d, "
+          "\"hkv\": %d, \"len\": %d, \"iters\": %d, \"causal\": %s, "
+          "\"tflops\": %.2f, \"tok_per_s\": %.1f, \"max_err\": %g, "
+          "\"max_rel\": %g}\n",
+          ok ? "true" : "false", b, hq, hkv, len, iters, causal ? "true" : "false",
+          r.tflops, r.tok_per_s, json_num(c.max_err), json_num(max_rel));
+      return ok ? 0 : 1;
     } else if (std::strcmp(cmd, "memcheck") == 0) {
       size_t bytes = argc > 2 ? std::strtoull(argv[2], nullptr, 10) : (size_t{1} << 30);
       int passes = argc > 3 ? std::atoi(argv[3]) : 1;
@@ -243,7 +281,8 @@ int main(int argc, char** argv) {
     } else if (std::strcmp(cmd, "serve") == 0) {
       // warm-pool worker: one line per request, one JSON line per reply
       //   vecadd <n> | busy <ms> | gemm [M N K] | mxgemm [M N K] |
-      //   mx4gemm [M N K] | attn [B HQ HKV L] | memcheck [BYTES] | ping | quit
+      //   mx4gemm [M N K] | attn [B HQ HKV L] | prefill [B HQ HKV L] |
+      //   memcheck [BYTES] | ping | quit
       std::string line;
       while (std::getline(std::cin, line)) {
         std::istringstream iss(line);
@@ -293,6 +332,17 @@ int main(int argc, char** argv) {
             std::printf(
                 "{\"ok\": %s, \"cmd\": \"attn\", \"batch\": %d, \"hq\": %d, "
                 "\"hkv\": %d, \"len\": %d, \"max_err\": %g, \"max_rel\": %g}\n",
+                ok ? "true" : "false", b, hq, hkv, len, json_num(c.max_err),
+                json_num(c.max_rel));
+          } else if (verb == "prefill") {
+            int b = 1, hq = 4, hkv = 2, len = 200, tb, tq, tk, tl;
+            if (iss >> tb >> tq >> tk >> tl) { b = tb; hq = tq; hkv = tk; len = tl; }
+            PrefillCheck c = run_prefill_check(b, hq, hkv, len);
+            bool ok = c.max_err == 0.0 && c.max_rel <= kPrefillRelBound;
+            std::printf(
+                "{\"ok\": %s, \"cmd\": \"prefill\", \"batch\": %d, \"hq\": %d, "
+                "\"hkv\": %d, \"len\": %d, \"causal\": true, \"max_err\": %g, "
+                "\"max_rel\": %g}\n",
                 ok ? "true" : "false", b, hq, hkv, len, json_num(c.max_err),
                 json_num(c.max_rel));
           } else if (verb == "memcheck") {

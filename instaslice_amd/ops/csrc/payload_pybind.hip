@@ -712,4 +712,153 @@ PYBIND11_MODULE(_payload, m) {
       py::arg("length") = 4096, py::arg("iters") = 10, py::arg("device") = 0,
       "timed decode attention on the selection pattern (device-filled cache, "
       "512 MiB of K and V at the default shape), 16 output rows checked exactly");
+
+  // ---- prefill attention -----------------------------------------------------
+
+  m.attr("PREFILL_ROWS") = payload::kPrefillRows;
+  m.attr("PREFILL_KEYS") = payload::kPrefillKeys;
+
+  // batch, hq, hkv, length of a prefill problem, or ValueError: the limits of
+  // detail::PrefillProblem, checked here before any HIP call
+  auto prefill_shape = [](const char* who, py::ssize_t B, py::ssize_t Hq,
+                          py::ssize_t Hkv, py::ssize_t L) {
+    std::string w(who);
+    if (B < 1 || Hq < 1 || Hkv < 1 || L < 1)
+      throw py::value_error(w + ": empty axis");
+    if (B > 65535 || Hq > 65535 || Hkv > 65535 || L > payload::kPrefillMaxLen)
+      throw py::value_error(w + ": shape too large");
+    if (Hq % Hkv != 0)
+      throw py::value_error(w + ": Hq must be a multiple of Hkv");
+    const unsigned long long blocks =
+        (static_cast<unsigned long long>(L) + payload::kPrefillRows - 1) /
+        payload::kPrefillRows;
+    if (static_cast<unsigned long long>(B) * Hq * blocks > 0x7FFFFFFFull)
+      throw py::value_error(w + ": shape too large");
+  };
+
+  m.def(
+      "attn_prefill",
+      [prefill_shape](f32_array q, f32_array k, f32_array v, bool causal,
+                      py::object scale, int device) {
+        const char* who = "attn_prefill";
+        if (q.ndim() != 4) throw py::value_error("attn_prefill: q must be (B,Hq,L,128)");
+        if (k.ndim() != 4 || v.ndim() != 4)
+          throw py::value_error("attn_prefill: k and v must be (B,Hkv,L,128)");
+        if (q.shape(3) != payload::kAttnD || k.shape(3) != payload::kAttnD)
+          throw py::value_error("attn_prefill: head dim must be 128");
+        for (int i = 0; i < 4; ++i)
+          if (k.shape(i) != v.shape(i))
+            throw py::value_error("attn_prefill: k and v differ in shape");
+        if (k.shape(0) != q.shape(0))
+          throw py::value_error("attn_prefill: q and k differ in batch");
+        if (k.shape(2) != q.shape(2))
+          throw py::value_error("attn_prefill: q and k differ in length");
+        const py::ssize_t B = q.shape(0), Hq = q.shape(1), Hkv = k.shape(1),
+                          L = q.shape(2);
+        prefill_shape(who, B, Hq, Hkv, L);
+        float sc = 1.0f / std::sqrt(static_cast<float>(payload::kAttnD));
+        if (!scale.is_none()) {
+          sc = scale.cast<float>();
+          if (!std::isfinite(sc)) throw py::value_error("attn_prefill: scale not finite");
+        }
+        const float* pq = q.data();
+        const float* pk = k.data();
+        const float* pv = v.data();
+        for (py::ssize_t i = 0, n = q.size(); i < n; ++i)
+          if (!std::isfinite(pq[i]))
+            throw py::value_error("attn_prefill: q has a non-finite element");
+        for (py::ssize_t i = 0, n = k.size(); i < n; ++i)
+          if (!std::isfinite(pk[i]) || !std::isfinite(pv[i]))
+            throw py::value_error("attn_prefill: k or v has a non-finite element");
+        py::array_t<float> o({B, Hq, L, static_cast<py::ssize_t>(payload::kAttnD)});
+        float* po = o.mutable_data();
+        {
+          py::gil_scoped_release rel;
+          payload::attn_prefill(pq, pk, pv, po, static_cast<int>(B),
+                                static_cast<int>(Hq), static_cast<int>(Hkv),
+                                static_cast<int>(L), causal, sc, device);
+        }
+        return o;
+      },
+      py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal") = true,
+      py::arg("scale") = py::none(), py::arg("device") = 0,
+      "o (B,Hq,L,128) float32 = softmax(scale q.k) v over the keys t <= i (causal) "
+      "or all L keys: grouped-query self-attention over a whole prompt, q "
+      "(B,Hq,L,128), k and v (B,Hkv,L,128) rounded to bf16, on the MFMA flash "
+      "kernel with K and V tiles staged through LDS; scale=None is 1/sqrt(128); "
+      "ValueError on an unsupported shape or a non-finite input or scale");
+
+  m.def(
+      "prefill_check_pattern",
+      [prefill_shape](int batch, int hq, int hkv, int length, bool causal) {
+        prefill_shape("prefill_check_pattern", batch, hq, hkv, length);
+        const py::ssize_t D = payload::kAttnD, B = batch, L = length;
+        py::array_t<float> q({B, static_cast<py::ssize_t>(hq), L, D});
+        py::array_t<float> e({B, static_cast<py::ssize_t>(hq), L, D});
+        py::array_t<float> k({B, static_cast<py::ssize_t>(hkv), L, D});
+        py::array_t<float> v({B, static_cast<py::ssize_t>(hkv), L, D});
+        payload::prefill_check_pattern(q.mutable_data(), k.mutable_data(),
+                                       v.mutable_data(), e.mutable_data(), batch, hq,
+                                       hkv, length, causal);
+        return py::make_tuple(q, k, v, e);
+      },
+      py::arg("batch"), py::arg("hq"), py::arg("hkv"), py::arg("length"),
+      py::arg("causal") = true,
+      "(q, k, v, expected) of the exact selection pattern: small integers, K zero "
+      "at the selected keys of a (sequence, kv head) (key 0 and every t with (t + "
+      "b + 2 g) % 5 == 0) and <= -16 elsewhere, expected = mean of v over the "
+      "selected keys a row sees; host only, no GPU");
+
+  m.def(
+      "run_prefill_check",
+      [prefill_shape](int batch, int hq, int hkv, int length, bool causal, int device) {
+        prefill_shape("run_prefill_check", batch, hq, hkv, length);
+        payload::PrefillCheck r;
+        {
+          py::gil_scoped_release rel;
+          r = payload::run_prefill_check(batch, hq, hkv, length, causal, device);
+        }
+        py::dict d;
+        d["max_err"] = r.max_err;
+        d["max_rel"] = r.max_rel;
+        return d;
+      },
+      py::arg("batch"), py::arg("hq"), py::arg("hkv"), py::arg("length"),
+      py::arg("causal") = true, py::arg("device") = 0,
+      "prefill attention self-check: max_err of the selection pattern (expect "
+      "exactly 0) and max_rel = max |o - fp64 ref| / max |v| of a dense pattern "
+      "(expect <= 2^-8)");
+
+  m.def(
+      "run_prefill",
+      [prefill_shape](int batch, int hq, int hkv, int length, int iters, bool causal,
+                      int device, int pattern) {
+        prefill_shape("run_prefill", batch, hq, hkv, length);
+        if (iters < 1) throw py::value_error("run_prefill: iters must be >= 1");
+        if (pattern != payload::kPrefillDense && pattern != payload::kPrefillSelection)
+          throw py::value_error("run_prefill: pattern must be 0 (dense) or 1 (selection)");
+        payload::PrefillResult r;
+        {
+          py::gil_scoped_release rel;
+          r = payload::run_prefill(batch, hq, hkv, length, iters, causal, device,
+                                   pattern);
+        }
+        py::dict d;
+        d["batch"] = batch;
+        d["hq"] = hq;
+        d["hkv"] = hkv;
+        d["len"] = length;
+        d["iters"] = iters;
+        d["causal"] = causal;
+        d["tflops"] = r.tflops;
+        d["tok_per_s"] = r.tok_per_s;
+        d["max_rel"] = r.max_rel;
+        return d;
+      },
+      py::arg("batch") = 8, py::arg("hq") = 64, py::arg("hkv") = 8,
+      py::arg("length") = 4096, py::arg("iters") = 10, py::arg("causal") = true,
+      py::arg("device") = 0, py::arg("pattern") = 0,
+      "timed prefill attention on the dense hash pattern (device-filled; pattern=1 "
+      "times the low-entropy selection pattern instead), TFLOP/s over the unmasked "
+      "pairs only, 16 spread output rows checked against fp64");
 }

@@ -443,3 +443,72 @@ def run_attn(profile_name: str, env: Optional[Dict[str, str]] = None,
         verdict["ok"] = False
         verdict["reason"] = f"payload exited {proc.returncode}"
     return verdict
+
+
+# ---- prefill ----------------------------------------------------------------
+
+# the numerics contract is decode's (bf16 weights, the normaliser summed from
+# the unrounded weights, one true division), so its bound carries over with
+# the derivation above ATTN_MAX_REL
+PREFILL_MAX_REL = ATTN_MAX_REL
+
+
+def judge_prefill(report: dict, profile_name: str) -> dict:
+    """Judge an `instaslice-payload prefill` report: "prefill" fails unless
+    `max_err` is a numeric zero, `max_rel` is a real number in [0, 2**-8],
+    `batch`, `hq`, `hkv`, `len`, `iters` are integer counts >= 1 and `causal`
+    is a bool. `tflops` and `tok_per_s` are carried and never judged. Pure; the
+    report's own `ok` is not trusted. ValueError on a profile name that does
+    not parse."""
+    parse_profile_name(profile_name)
+    clean = (_is_zero(report.get("max_err"))
+             and _is_real(report.get("max_rel"))
+             and 0 <= report["max_rel"] <= PREFILL_MAX_REL
+             and all(_is_count(report.get(key)) and report[key] >= 1
+                     for key in ("batch", "hq", "hkv", "len", "iters"))
+             and isinstance(report.get("causal"), bool))
+    failed = [] if clean else ["prefill"]
+    return {"ok": not failed, "failed": failed, "profile": profile_name,
+            "report": report}
+
+
+def run_prefill(profile_name: str, env: Optional[Dict[str, str]] = None,
+                runner: Callable = subprocess.run) -> dict:
+    """Run `instaslice-payload prefill` (default shape and iterations, causal)
+    in a fresh child with `env` and judge its report, with the same contract
+    as `run_attn`: every way the child can fail comes back as `ok: False` with
+    a `reason`, and only an unparseable profile name raises (ValueError)."""
+    parse_profile_name(profile_name)
+    child_env = dict(os.environ)
+    child_env.update({k: str(v) for k, v in (env or {}).items()})
+    try:
+        proc = runner([BIN_PATH, "prefill"], capture_output=True, text=True,
+                      timeout=CHILD_TIMEOUT_S, env=child_env)
+    except FileNotFoundError:
+        return _not_run(profile_name, f"payload binary not found: {BIN_PATH}")
+    except subprocess.TimeoutExpired:
+        return _not_run(profile_name,
+                        f"prefill timed out after {CHILD_TIMEOUT_S:.0f} s")
+    except OSError as e:
+        return _not_run(profile_name, f"could not start payload binary: {e}")
+
+    lines = [ln for ln in (proc.stdout or "").splitlines() if ln.strip()]
+    try:
+        report = json.loads(lines[-1]) if lines else None
+    except ValueError:
+        report = None
+    if not isinstance(report, dict):
+        tail = (proc.stdout or "").strip()[-200:]
+        return _not_run(profile_name,
+                        f"non-JSON output (exit {proc.returncode}): {tail!r}")
+    if "max_err" not in report:
+        # the binary's catch-all error line: {"ok": false, "error": "..."}
+        return _not_run(profile_name,
+                        f"prefill failed (exit {proc.returncode}): "
+                        f"{report.get('error', 'no report fields')}", report)
+    verdict = judge_prefill(report, profile_name)
+    if proc.returncode != 0:
+        # clean-looking fields do not outvote a non-zero exit
+        verdict["ok"] = False
+        verdict["reason"] = f"payload exited {proc.returncode}"
+    return verdict
