@@ -20,7 +20,8 @@
 // M, N to 128 and K to 64: the kernel has no edge branch and no address
 // outside its buffers for any shape. Only the M x N region is copied back.
 //
-// Included by payload_core.hpp (needs its HIP_CHECK and kBlock).
+// Included by payload_core.hpp (needs its HIP_CHECK, kBlock, detail::DeviceBuffer
+// and detail::Event).
 
 #pragma once
 
@@ -159,29 +160,7 @@ struct GemmResult {
 
 namespace detail {
 
-// hipFree / hipEventDestroy on every exit path, throws included
-struct DeviceBuffer {
-  void* p = nullptr;
-  DeviceBuffer() = default;
-  DeviceBuffer(const DeviceBuffer&) = delete;
-  DeviceBuffer& operator=(const DeviceBuffer&) = delete;
-  ~DeviceBuffer() {
-    if (p) (void)hipFree(p);
-  }
-  void alloc(size_t bytes) { HIP_CHECK(hipMalloc(&p, bytes)); }
-  template <typename T>
-  T* as() const { return static_cast<T*>(p); }
-};
-
-struct Event {
-  hipEvent_t e = nullptr;
-  Event() { HIP_CHECK(hipEventCreate(&e)); }
-  Event(const Event&) = delete;
-  Event& operator=(const Event&) = delete;
-  ~Event() {
-    if (e) (void)hipEventDestroy(e);
-  }
-};
+// DeviceBuffer and Event are payload_core.hpp's
 
 inline size_t round_up(size_t v, size_t m) { return (v + m - 1) / m * m; }
 

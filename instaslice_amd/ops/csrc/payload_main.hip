@@ -6,9 +6,16 @@
 // exactly the device set a real pod would see. Prints one JSON line.
 //
 //   instaslice-payload info
-//   instaslice-payload vecadd [N]
-//   instaslice-payload membw [BYTES] [ITERS]
-//   instaslice-payload busy [MS]
+//   instaslice-payload vecadd [N]             N >= 1 floats, operands derived
+//                                             from the element index; exit 1
+//                                             unless max_err == 0
+//   instaslice-payload membw [BYTES [ITERS [BLOCKS [NT]]]]
+//                                             streaming copy, then the
+//                                             destination checked against the
+//                                             index-derived pattern; exit 1
+//                                             iff bad_units != 0
+//   instaslice-payload busy [MS]              MS finite, in 0 .. 60000; prints
+//                                             the device-side elapsed_ms
 //   instaslice-payload census
 //   instaslice-payload gemm [M N K [ITERS]]   bf16 MFMA GEMM, exact-checked
 //                                             and timed (default 4096 4096
@@ -73,8 +80,9 @@
 //                                             line; XCDS (0 or absent: not
 //                                             checked) is the XCD count the
 //                                             partition should show. Only
-//                                             vecadd, gemm and xcds are
-//                                             judged; rates are reported.
+//                                             vecadd, gemm, xcds and membw's
+//                                             bad_units are judged; rates are
+//                                             reported.
 //                                             exit 1 iff "failed" is non-empty
 //   instaslice-payload serve      (persistent worker: commands on stdin,
 //                                  one JSON line per command on stdout —
@@ -101,6 +109,23 @@ using namespace payload;
 
 // JSON has no inf/nan: an error that is not finite prints as a huge number
 static double json_num(double v) { return std::isfinite(v) ? v : 1e300; }
+
+static bool print_vecadd(size_t n) {
+  double err = run_vecadd(n);
+  std::printf("{\"ok\": %s, \"cmd\": \"vecadd\", \"n\": %zu, \"max_err\": %g}\n",
+              err == 0.0 ? "true" : "false", n, json_num(err));
+  return err == 0.0;
+}
+
+// "nan" and "inf" parse as such and are then rejected by run_busy
+static void print_busy(const char* ms_text) {
+  double ms = std::strtod(ms_text, nullptr);
+  BusyResult r = run_busy(ms);
+  std::printf(
+      "{\"ok\": true, \"cmd\": \"busy\", \"ms\": %.1f, \"elapsed_ms\": %.3f, "
+      "\"iters\": %llu, \"guard_hit\": %s}\n",
+      ms, r.elapsed_ms, r.iters, r.guard_hit ? "true" : "false");
+}
 
 // one JSON line for a memcheck result; bad_bits is a string because a u64
 // does not survive a JSON double
@@ -136,24 +161,23 @@ int main(int argc, char** argv) {
       std::printf("}\n");
     } else if (std::strcmp(cmd, "vecadd") == 0) {
       size_t n = argc > 2 ? std::strtoull(argv[2], nullptr, 10) : (1 << 24);
-      double err = run_vecadd(n);
-      std::printf("{\"ok\": %s, \"cmd\": \"vecadd\", \"n\": %zu, \"max_err\": %g}\n",
-                  err == 0.0 ? "true" : "false", n, err);
-      return err == 0.0 ? 0 : 1;
+      return print_vecadd(n) ? 0 : 1;
     } else if (std::strcmp(cmd, "membw") == 0) {
       size_t bytes = argc > 2 ? std::strtoull(argv[2], nullptr, 10) : (size_t{1} << 30);
       int iters = argc > 3 ? std::atoi(argv[3]) : 10;
       int blocks = argc > 4 ? std::atoi(argv[4]) : 0;
       bool nt = argc > 5 && std::atoi(argv[5]) != 0;
-      double gbs = run_membw(bytes, iters, 0, blocks, nt);
+      MembwResult r = run_membw_check(bytes, iters, 0, blocks, nt);
+      bool ok = r.bad_units == 0;
       std::printf(
-          "{\"ok\": true, \"cmd\": \"membw\", \"bytes\": %zu, \"iters\": %d, "
-          "\"blocks\": %d, \"nontemporal\": %s, \"gb_per_s\": %.1f}\n",
-          bytes, iters, blocks, nt ? "true" : "false", gbs);
+          "{\"ok\": %s, \"cmd\": \"membw\", \"bytes\": %zu, \"iters\": %d, "
+          "\"blocks\": %d, \"nontemporal\": %s, \"gb_per_s\": %.1f, "
+          "\"bad_units\": %llu}\n",
+          ok ? "true" : "false", bytes, iters, blocks, nt ? "true" : "false", r.gb_s,
+          r.bad_units);
+      return ok ? 0 : 1;
     } else if (std::strcmp(cmd, "busy") == 0) {
-      double ms = argc > 2 ? std::atof(argv[2]) : 100.0;
-      run_busy(ms);
-      std::printf("{\"ok\": true, \"cmd\": \"busy\", \"ms\": %.1f}\n", ms);
+      print_busy(argc > 2 ? argv[2] : "100");
     } else if (std::strcmp(cmd, "census") == 0) {
       auto c = run_xcd_census();
       std::printf("{\"ok\": true, \"cmd\": \"census\", \"per_xcd\": [");
@@ -254,13 +278,15 @@ int main(int argc, char** argv) {
         if (v) ++xcds;
       double vecadd_err = run_vecadd(1 << 20);
       double gemm_err = run_gemm_check(96, 160, 224);
-      double gbs = run_membw(size_t{256} << 20, 5);
+      MembwResult mb = run_membw_check(size_t{256} << 20, 5);
+      double gbs = mb.gb_s;
       GemmResult r = run_gemm(4096, 4096, 1024, 5);
       if (r.max_err > gemm_err) gemm_err = r.max_err;
       bool bad_vecadd = vecadd_err != 0.0;
       bool bad_gemm = gemm_err != 0.0;
       bool bad_xcds = expected > 0 && xcds != expected;
-      bool ok = !(bad_vecadd || bad_gemm || bad_xcds);
+      bool bad_membw = mb.bad_units != 0;
+      bool ok = !(bad_vecadd || bad_gemm || bad_xcds || bad_membw);
       std::printf("{\"ok\": %s, \"cmd\": \"verify\", \"xcds_expected\": %d, "
                   "\"xcds_visible\": %d, \"per_xcd\": [",
                   ok ? "true" : "false", expected, xcds);
@@ -268,14 +294,16 @@ int main(int argc, char** argv) {
       int per = xcds > 0 ? xcds : 1;
       std::printf(
           "], \"cu_count\": %d, \"total_mem_gb\": %.1f, \"vecadd_max_err\": %g, "
-          "\"gemm_max_err\": %g, \"gb_per_s\": %.1f, \"tflops\": %.2f, "
-          "\"gb_per_s_per_xcd\": %.1f, \"tflops_per_xcd\": %.2f, \"failed\": [",
+          "\"gemm_max_err\": %g, \"membw_bad_units\": %llu, \"gb_per_s\": %.1f, "
+          "\"tflops\": %.2f, \"gb_per_s_per_xcd\": %.1f, \"tflops_per_xcd\": %.2f, "
+          "\"failed\": [",
           info.cu_count, info.total_mem_gb, json_num(vecadd_err),
-          json_num(gemm_err), gbs, r.tflops, gbs / per, r.tflops / per);
+          json_num(gemm_err), mb.bad_units, gbs, r.tflops, gbs / per, r.tflops / per);
       const char* sep = "";
       if (bad_vecadd) { std::printf("%s\"vecadd\"", sep); sep = ", "; }
       if (bad_gemm) { std::printf("%s\"gemm\"", sep); sep = ", "; }
       if (bad_xcds) { std::printf("%s\"xcds\"", sep); sep = ", "; }
+      if (bad_membw) { std::printf("%s\"membw\"", sep); sep = ", "; }
       std::printf("]}\n");
       return ok ? 0 : 1;
     } else if (std::strcmp(cmd, "serve") == 0) {
@@ -296,10 +324,7 @@ int main(int argc, char** argv) {
           } else if (verb == "vecadd") {
             size_t n = 1 << 20;
             iss >> n;
-            double err = run_vecadd(n);
-            std::printf(
-                "{\"ok\": %s, \"cmd\": \"vecadd\", \"n\": %zu, \"max_err\": %g}\n",
-                err == 0.0 ? "true" : "false", n, err);
+            print_vecadd(n);
           } else if (verb == "gemm") {
             int m = 96, n = 160, k = 224, tm, tn, tk;
             if (iss >> tm >> tn >> tk) { m = tm; n = tn; k = tk; }
@@ -350,10 +375,9 @@ int main(int argc, char** argv) {
             iss >> bytes;
             print_memcheck(run_memcheck(bytes));
           } else if (verb == "busy") {
-            double ms = 10.0;
+            std::string ms = "10";  // as text: operator>> does not read "nan"
             iss >> ms;
-            run_busy(ms);
-            std::printf("{\"ok\": true, \"cmd\": \"busy\", \"ms\": %.1f}\n", ms);
+            print_busy(ms.c_str());
           } else {
             std::printf("{\"ok\": false, \"error\": \"unknown verb\"}\n");
           }

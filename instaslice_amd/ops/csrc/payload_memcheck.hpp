@@ -46,8 +46,8 @@
 // anything is re-read, and that is what pushes the data out to HBM for large
 // buffers.
 //
-// Included by payload_core.hpp (needs its HIP_CHECK, kBlock and grid_for, and
-// detail::DeviceBuffer / detail::Event from payload_gemm.hpp).
+// Included by payload_core.hpp (needs its HIP_CHECK, kBlock, grid_for,
+// detail::DeviceBuffer and detail::Event).
 
 #pragma once
 

@@ -14,7 +14,7 @@ namespace py = pybind11;
 
 PYBIND11_MODULE(_payload, m) {
   m.doc() = "gfx950 HIP payload kernels (vecadd / membw / busy / xcd census / gemm / "
-            "mxgemm / mx4gemm / memcheck / attn)";
+            "mxgemm / mx4gemm / memcheck / attn / prefill)";
 
   m.def("device_count", &payload::device_count,
         "Number of visible HIP devices (0 if no GPU/driver)");
@@ -26,7 +26,8 @@ PYBIND11_MODULE(_payload, m) {
         return payload::run_vecadd(n, device);
       },
       py::arg("n") = (1 << 20), py::arg("device") = 0,
-      "c = a + b over n floats on `device`; returns max abs error (expect 0)");
+      "c = a + b over n >= 1 floats on `device`, operands derived from the element "
+      "index; returns max abs error (expect 0)");
 
   m.def(
       "run_membw",
@@ -36,16 +37,51 @@ PYBIND11_MODULE(_payload, m) {
       },
       py::arg("bytes") = (size_t{1} << 30), py::arg("iters") = 10,
       py::arg("device") = 0,
-      "streaming-copy bandwidth probe; returns GB/s (read+write)");
+      "streaming-copy bandwidth probe; returns GB/s (read+write); RuntimeError if "
+      "the copy's destination does not hold the pattern");
+
+  m.def(
+      "run_membw_check",
+      [](size_t bytes, int iters, int device, int blocks, bool nontemporal) {
+        payload::MembwResult r;
+        {
+          py::gil_scoped_release rel;
+          r = payload::run_membw_check(bytes, iters, device, blocks, nontemporal);
+        }
+        py::dict d;
+        d["gb_per_s"] = r.gb_s;
+        d["bad_units"] = r.bad_units;
+        return d;
+      },
+      py::arg("bytes") = (size_t{1} << 30), py::arg("iters") = 10,
+      py::arg("device") = 0, py::arg("blocks") = 0, py::arg("nontemporal") = false,
+      "streaming-copy bandwidth probe with its check: GB/s (read+write) and the "
+      "number of 16-byte units of the destination that differ from the "
+      "index-derived pattern (expect 0); blocks=0 is the default grid");
 
   m.def(
       "run_busy",
-      [](double ms, int device) {
-        py::gil_scoped_release rel;
-        payload::run_busy(ms, device);
+      [](double ms, int device, unsigned long long max_iters) {
+        payload::BusyResult r;
+        {
+          py::gil_scoped_release rel;
+          r = payload::run_busy(ms, device, max_iters);
+        }
+        py::dict d;
+        d["elapsed_ms"] = r.elapsed_ms;
+        d["iters"] = r.iters;
+        d["guard_hit"] = r.guard_hit;
+        return d;
       },
-      py::arg("ms") = 100.0, py::arg("device") = 0,
-      "occupy the device with a bounded spin for ~ms (sleep-pod payload)");
+      py::arg("ms") = 100.0, py::arg("device") = 0, py::arg("max_iters") = 0,
+      "occupy the device with a bounded spin for ~ms (sleep-pod payload), ms "
+      "finite and in 0 .. 60000; max_iters bounds the spin's trips (0: the "
+      "built-in bound); returns the device-side elapsed_ms and iters of block "
+      "0's first lane and whether the iteration guard ended its spin");
+
+  m.def("grid_for", &payload::grid_for, py::arg("n4"),
+        "the default grid for n4 float4s: ceil(n4 / 256) in 1 .. 65535; host only, "
+        "no GPU");
 
   m.def(
       "run_xcd_census",
@@ -79,6 +115,57 @@ PYBIND11_MODULE(_payload, m) {
   // other-dtype array is copied into a contiguous float32 one, and anything
   // that cannot be converted is a TypeError
   using f32_array = py::array_t<float, py::array::c_style | py::array::forcecast>;
+  using u32_array = py::array_t<uint32_t, py::array::c_style | py::array::forcecast>;
+
+  m.def(
+      "vecadd",
+      [](f32_array a, f32_array b, int device, int blocks) {
+        if (a.ndim() != 1 || b.ndim() != 1)
+          throw py::value_error("vecadd: a and b must be 1-D");
+        if (a.shape(0) != b.shape(0))
+          throw py::value_error("vecadd: a and b differ in length");
+        if (a.shape(0) < 1) throw py::value_error("vecadd: empty operand");
+        const size_t n = static_cast<size_t>(a.shape(0));
+        py::array_t<float> c(static_cast<py::ssize_t>(n));
+        const float* pa = a.data();
+        const float* pb = b.data();
+        float* pc = c.mutable_data();
+        size_t guard_changed;
+        {
+          py::gil_scoped_release rel;
+          guard_changed = payload::vecadd(pa, pb, pc, n, device, blocks);
+        }
+        return py::make_tuple(c, guard_changed);
+      },
+      py::arg("a"), py::arg("b"), py::arg("device") = 0, py::arg("blocks") = 0,
+      "(c, guard_changed): c float32 (n,) = a + b on the vecadd kernel, a and b "
+      "1-D float32 of equal length n >= 1, zero-padded to whole float4s; blocks=0 "
+      "is the default grid, blocks > 0 forces that grid; guard_changed counts the "
+      "bytes the kernel changed in the 4 KiB guards around the destination "
+      "(expect 0)");
+
+  m.def(
+      "stream_copy",
+      [](u32_array x, bool nontemporal, int device, int blocks) {
+        if (x.ndim() != 1) throw py::value_error("stream_copy: x must be 1-D");
+        if (x.shape(0) < 1) throw py::value_error("stream_copy: empty operand");
+        const size_t n = static_cast<size_t>(x.shape(0));
+        py::array_t<uint32_t> y(static_cast<py::ssize_t>(n));
+        const uint32_t* px = x.data();
+        uint32_t* py_ = y.mutable_data();
+        size_t guard_changed;
+        {
+          py::gil_scoped_release rel;
+          guard_changed = payload::stream_copy(px, py_, n, nontemporal, device, blocks);
+        }
+        return py::make_tuple(y, guard_changed);
+      },
+      py::arg("x"), py::arg("nontemporal") = false, py::arg("device") = 0,
+      py::arg("blocks") = 0,
+      "(y, guard_changed): y uint32 (n,) = x through the streaming-copy kernel of "
+      "the bandwidth probe, or its nontemporal variant; x 1-D uint32 of length n "
+      ">= 1 (words, so that every bit pattern survives the binding); blocks and "
+      "guard_changed as in vecadd");
 
   m.def(
       "to_bf16",

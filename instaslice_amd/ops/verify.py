@@ -10,8 +10,10 @@ judges the report against a profile name such as `cpx-1x36`:
     verdict = verify.run("cpx-1x36", env={"ROCR_VISIBLE_DEVICES": uuid})
     verdict["ok"], verdict["failed"]
 
-Judged: vecadd and GEMM exactness (max error 0) and the visible XCD count.
-Bandwidth, TFLOP/s, CU count and memory size are carried in the report and
+Judged: vecadd and GEMM exactness (max error 0), the visible XCD count and
+the bandwidth probe's copy (`membw_bad_units`, the 16-byte units of its
+destination that do not hold the pattern, must be 0: a rate from a copy that
+did not copy proves nothing). Bandwidth, TFLOP/s, CU count and memory size are carried in the report and
 never judged: there are no measured per-partition values to hold them to.
 
 A live verifier holds the device for its run (a second or two), which blocks
@@ -95,6 +97,8 @@ def judge(report: dict, profile_name: str) -> dict:
         failed.append("gemm")
     if report.get("xcds_visible") != want:
         failed.append("xcds")
+    if not _is_zero(report.get("membw_bad_units")):
+        failed.append("membw")
     return {"ok": not failed, "failed": failed, "profile": profile_name,
             "report": report}
 

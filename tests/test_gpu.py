@@ -86,10 +86,18 @@ class TestPayloadKernels:
         # numerics contract: HIP kernel vs plain fp32 reference
         import numpy as np
 
-        a = np.full(1024, 1.25, dtype=np.float32)
-        b = np.full(1024, 2.5, dtype=np.float32)
-        ref = a + b
-        assert float(ref[0]) == 3.75  # what the kernel asserts against
+        rng = np.random.default_rng(1024)
+        a = rng.standard_normal(1024).astype(np.float32)
+        b = (rng.standard_normal(1024) * 1e3).astype(np.float32)
+        ref = a + b  # one correctly rounded fp32 add per element
+        c, guard_changed = payload.vecadd(a, b)
+        assert c.dtype == np.float32 and c.shape == ref.shape
+        assert np.array_equal(c.view(np.uint32), ref.view(np.uint32))
+        assert guard_changed == 0
+        # the constant operands of the first version of this test
+        c, _ = payload.vecadd(np.full(1024, 1.25, dtype=np.float32),
+                              np.full(1024, 2.5, dtype=np.float32))
+        assert np.array_equal(c, np.full(1024, 3.75, dtype=np.float32))
         assert payload.run_vecadd(1024) == 0.0
 
     def test_membw_sane(self, payload):

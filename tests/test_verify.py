@@ -17,6 +17,7 @@ def report(**over):
         "ok": True, "cmd": "verify", "xcds_expected": 1, "xcds_visible": 1,
         "per_xcd": [0, 0, 0, 2048, 0, 0, 0, 0], "cu_count": 32,
         "total_mem_gb": 36.0, "vecadd_max_err": 0, "gemm_max_err": 0,
+        "membw_bad_units": 0,
         "gb_per_s": 700.0, "tflops": 90.0, "gb_per_s_per_xcd": 700.0,
         "tflops_per_xcd": 90.0, "failed": [],
     }
@@ -67,6 +68,18 @@ def test_judge_vecadd_and_missing_fields():
     rep = report()
     del rep["gemm_max_err"]
     assert verify.judge(rep, "cpx-1x36")["failed"] == ["gemm"]
+
+
+def test_judge_membw_bad_units():
+    v = verify.judge(report(membw_bad_units=3), "cpx-1x36")
+    assert v["ok"] is False and v["failed"] == ["membw"]
+    rep = report()
+    del rep["membw_bad_units"]
+    v = verify.judge(rep, "cpx-1x36")
+    assert v["ok"] is False and v["failed"] == ["membw"]
+    # a count that is not a number is not a zero
+    assert verify.judge(report(membw_bad_units="0"), "cpx-1x36")["failed"] == ["membw"]
+    assert verify.judge(report(membw_bad_units=None), "cpx-1x36")["failed"] == ["membw"]
 
 
 def test_judge_rates_are_not_judged():
