@@ -94,15 +94,8 @@ def build(force: bool = False) -> None:
 
     # 3. _payload pybind module (gfx950 device code)
     src = ops_dir / "csrc" / "payload_pybind.hip"
-    hdr = ops_dir / "csrc" / "payload_core.hpp"
-    hdr_gemm = ops_dir / "csrc" / "payload_gemm.hpp"  # included by payload_core
-    hdr_memcheck = ops_dir / "csrc" / "payload_memcheck.hpp"  # likewise
-    hdr_mxgemm = ops_dir / "csrc" / "payload_mxgemm.hpp"  # likewise
-    hdr_mxfp4 = ops_dir / "csrc" / "payload_mxfp4.hpp"  # likewise
-    hdr_attn = ops_dir / "csrc" / "payload_attn.hpp"  # likewise
-    hdr_prefill = ops_dir / "csrc" / "payload_prefill.hpp"  # likewise
-    payload_hdrs = [hdr, hdr_gemm, hdr_memcheck, hdr_mxgemm, hdr_mxfp4, hdr_attn,
-                    hdr_prefill]
+    # payload_core.hpp and every header it includes
+    payload_hdrs = sorted((ops_dir / "csrc").glob("*.hpp"))
     out = ops_dir / f"_payload{EXT}"
     if force or not newer(out, [src, *payload_hdrs], ARCH):
         run([HIPCC, f"--offload-arch={ARCH}", "-shared", *common,

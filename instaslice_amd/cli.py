@@ -375,113 +375,63 @@ def cmd_payload(args) -> int:
     return subprocess.call([bin_path] + args.payload_args)
 
 
-def cmd_verify(args) -> int:
-    """Run the payload probes inside the visible partition and judge them
-    against the requested profile; prints the judged JSON, exit 0 iff ok."""
+def _probe(args, run_name: str, **kwargs) -> int:
+    """Call `verify.<run_name>(args.profile, env=..., **kwargs)` (looked up on
+    the module when called), print the judged JSON; exit 0 iff ok."""
     from instaslice_amd.ops import verify
 
     env = {}
     if args.visible_devices is not None:
         env["ROCR_VISIBLE_DEVICES"] = args.visible_devices
     try:
-        verdict = verify.run(args.profile, env=env)
+        verdict = getattr(verify, run_name)(args.profile, env=env, **kwargs)
     except ValueError as e:
         verdict = {"ok": False, "failed": [], "profile": args.profile,
                    "reason": str(e), "report": None}
     print(json.dumps(verdict))
     return 0 if verdict["ok"] else 1
+
+
+def cmd_verify(args) -> int:
+    """Run the payload probes inside the visible partition and judge them
+    against the requested profile; prints the judged JSON, exit 0 iff ok."""
+    return _probe(args, "run")
 
 
 def cmd_memcheck(args) -> int:
     """Sweep a buffer of the visible partition's memory with the memcheck
     payload and judge it against the requested profile; prints the judged
     JSON, exit 0 iff ok."""
-    from instaslice_amd.ops import verify
-
-    env = {}
-    if args.visible_devices is not None:
-        env["ROCR_VISIBLE_DEVICES"] = args.visible_devices
-    try:
-        verdict = verify.run_memcheck(args.profile, env=env, gb=args.gb,
-                                      fraction=args.fraction,
-                                      passes=args.passes)
-    except ValueError as e:
-        verdict = {"ok": False, "failed": [], "profile": args.profile,
-                   "reason": str(e), "report": None}
-    print(json.dumps(verdict))
-    return 0 if verdict["ok"] else 1
+    return _probe(args, "run_memcheck", gb=args.gb, fraction=args.fraction,
+                  passes=args.passes)
 
 
 def cmd_mxgemm(args) -> int:
     """Run the MXFP8 block-scaled GEMM payload inside the visible partition
     and judge it against the requested profile; prints the judged JSON, exit
     0 iff ok."""
-    from instaslice_amd.ops import verify
-
-    env = {}
-    if args.visible_devices is not None:
-        env["ROCR_VISIBLE_DEVICES"] = args.visible_devices
-    try:
-        verdict = verify.run_mxgemm(args.profile, env=env)
-    except ValueError as e:
-        verdict = {"ok": False, "failed": [], "profile": args.profile,
-                   "reason": str(e), "report": None}
-    print(json.dumps(verdict))
-    return 0 if verdict["ok"] else 1
+    return _probe(args, "run_mxgemm")
 
 
 def cmd_mx4gemm(args) -> int:
     """Run the MXFP4 block-scaled GEMM payload inside the visible partition
     and judge it against the requested profile; prints the judged JSON, exit
     0 iff ok."""
-    from instaslice_amd.ops import verify
-
-    env = {}
-    if args.visible_devices is not None:
-        env["ROCR_VISIBLE_DEVICES"] = args.visible_devices
-    try:
-        verdict = verify.run_mx4gemm(args.profile, env=env)
-    except ValueError as e:
-        verdict = {"ok": False, "failed": [], "profile": args.profile,
-                   "reason": str(e), "report": None}
-    print(json.dumps(verdict))
-    return 0 if verdict["ok"] else 1
+    return _probe(args, "run_mx4gemm")
 
 
 def cmd_attn(args) -> int:
     """Run the KV-cache decode attention payload inside the visible partition
     and judge it against the requested profile; prints the judged JSON, exit
     0 iff ok."""
-    from instaslice_amd.ops import verify
-
-    env = {}
-    if args.visible_devices is not None:
-        env["ROCR_VISIBLE_DEVICES"] = args.visible_devices
-    try:
-        verdict = verify.run_attn(args.profile, env=env)
-    except ValueError as e:
-        verdict = {"ok": False, "failed": [], "profile": args.profile,
-                   "reason": str(e), "report": None}
-    print(json.dumps(verdict))
-    return 0 if verdict["ok"] else 1
+    return _probe(args, "run_attn")
 
 
 def cmd_prefill(args) -> int:
     """Run the causal prefill attention payload inside the visible partition
     and judge it against the requested profile; prints the judged JSON, exit
     0 iff ok."""
-    from instaslice_amd.ops import verify
-
-    env = {}
-    if args.visible_devices is not None:
-        env["ROCR_VISIBLE_DEVICES"] = args.visible_devices
-    try:
-        verdict = verify.run_prefill(args.profile, env=env)
-    except ValueError as e:
-        verdict = {"ok": False, "failed": [], "profile": args.profile,
-                   "reason": str(e), "report": None}
-    print(json.dumps(verdict))
-    return 0 if verdict["ok"] else 1
+    return _probe(args, "run_prefill")
 
 
 def main(argv=None) -> int:

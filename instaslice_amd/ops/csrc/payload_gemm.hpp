@@ -164,21 +164,46 @@ namespace detail {
 
 inline size_t round_up(size_t v, size_t m) { return (v + m - 1) / m * m; }
 
-// Padded operands on the host plus their device images and the padded C.
-struct GemmProblem {
+// What the three GEMM payloads' problems share: the shape, the padded shape
+// and the padded C. Each problem adds its padded operands, upload() and
+// launch().
+struct GemmShape {
   int M, N, K;
   size_t Mp, Np, Kp;
-  std::vector<uint16_t> a, bt;  // Mp x Kp, Np x Kp, zero-padded
-  DeviceBuffer da, dbt, dc;
+  DeviceBuffer dc;
 
-  GemmProblem(int m, int n, int k) : M(m), N(n), K(k) {
+  // who: the name used in messages; bk: the kernel's K-step in elements;
+  // max_kp: the largest Kp the kernel's 32-bit offsets allow
+  GemmShape(const std::string& who, int m, int n, int k, size_t bk, size_t max_kp)
+      : M(m), N(n), K(k) {
     if (m < 1 || n < 1 || k < 1)
-      throw std::invalid_argument("gemm: M, N and K must be >= 1");
+      throw std::invalid_argument(who + ": M, N and K must be >= 1");
     Mp = round_up(m, kGemmBM);
     Np = round_up(n, kGemmBN);
-    Kp = round_up(k, kGemmBK);
-    if (Mp / kGemmBM > 65535 || Np > 0x7FFFFF80u || Kp > 0x7FFFFFC0u)
-      throw std::invalid_argument("gemm: shape too large");
+    Kp = round_up(k, bk);
+    if (Mp / kGemmBM > 65535 || Np > 0x7FFFFF80u || Kp > max_kp)
+      throw std::invalid_argument(who + ": shape too large");
+  }
+
+  // grid = (Np / 128, Mp / 128) for all three kernels
+  dim3 grid() const {
+    return dim3(static_cast<unsigned>(Np / kGemmBN), static_cast<unsigned>(Mp / kGemmBM));
+  }
+
+  // the un-padded M x N region, row-major, into c
+  void download(float* c) const {
+    HIP_CHECK(hipMemcpy2D(c, static_cast<size_t>(N) * sizeof(float), dc.p,
+                          Np * sizeof(float), static_cast<size_t>(N) * sizeof(float),
+                          M, hipMemcpyDeviceToHost));
+  }
+};
+
+// Padded operands on the host plus their device images.
+struct GemmProblem : GemmShape {
+  std::vector<uint16_t> a, bt;  // Mp x Kp, Np x Kp, zero-padded
+  DeviceBuffer da, dbt;
+
+  GemmProblem(int m, int n, int k) : GemmShape("gemm", m, n, k, kGemmBK, 0x7FFFFFC0u) {
     a.assign(Mp * Kp, 0);
     bt.assign(Np * Kp, 0);
   }
@@ -195,17 +220,9 @@ struct GemmProblem {
   }
 
   void launch() const {
-    dim3 grid(static_cast<unsigned>(Np / kGemmBN), static_cast<unsigned>(Mp / kGemmBM));
-    hipLaunchKernelGGL(gemm_bf16_kernel, grid, dim3(kBlock), 0, 0,
+    hipLaunchKernelGGL(gemm_bf16_kernel, grid(), dim3(kBlock), 0, 0,
                        da.as<const uint16_t>(), dbt.as<const uint16_t>(),
                        dc.as<float>(), static_cast<int>(Np), static_cast<int>(Kp));
-  }
-
-  // the un-padded M x N region, row-major, into c
-  void download(float* c) const {
-    HIP_CHECK(hipMemcpy2D(c, static_cast<size_t>(N) * sizeof(float), dc.p,
-                          Np * sizeof(float), static_cast<size_t>(N) * sizeof(float),
-                          M, hipMemcpyDeviceToHost));
   }
 };
 
@@ -232,6 +249,11 @@ inline int64_t pattern_dot(int i, int j, int K) {
   return s;
 }
 
+inline double pattern_err(float got, int i, int j, int K) {
+  return std::fabs(static_cast<double>(got) -
+                   static_cast<double>(pattern_dot(i, j, K)));
+}
+
 // a NaN result is an error, not a skipped comparison
 inline void note_err(double& max_err, double e) {
   if (std::isnan(e)) e = INFINITY;
@@ -242,6 +264,64 @@ inline void require_exact_k(int k, const char* who) {
   if (k > kGemmMaxExactK)
     throw std::invalid_argument(std::string(who) + ": K must be <= 1024 "
                                 "(the integer pattern is exact in fp32 only up to there)");
+}
+
+// The three drivers below serve every GEMM payload. P is a problem: a
+// GemmShape with upload(device) and launch(). PatternErr is |got - exact| of
+// output (i, j) of the problem's own pattern at depth K.
+using PatternErr = double (*)(float got, int i, int j, int K);
+
+// upload, one launch, the M x N result into c
+template <class P>
+void run_once(P& p, int device, float* c) {
+  p.upload(device);
+  p.launch();
+  HIP_CHECK(hipGetLastError());
+  p.download(c);
+}
+
+// max err over the whole M x N result of a problem filled with its pattern
+template <class P>
+double run_full_check(P& p, int device, PatternErr err) {
+  std::vector<float> host(static_cast<size_t>(p.M) * p.N);
+  run_once(p, device, host.data());
+  double max_err = 0;
+  for (int i = 0; i < p.M; ++i)
+    for (int j = 0; j < p.N; ++j)
+      note_err(max_err, err(host[static_cast<size_t>(i) * p.N + j], i, j, p.K));
+  return max_err;
+}
+
+// One warm-up launch, `iters` launches between events, then 256 fixed, spread
+// output elements are checked exactly, so a fast wrong kernel cannot report a
+// rate. FLOPs are counted as 2 M N K.
+template <class P>
+GemmResult run_timed(P& p, int iters, int device, PatternErr err) {
+  p.upload(device);
+  p.launch();  // warmup
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipDeviceSynchronize());
+  float ms = 0;
+  {
+    Event t0, t1;
+    HIP_CHECK(hipEventRecord(t0.e, 0));
+    for (int i = 0; i < iters; ++i) p.launch();
+    HIP_CHECK(hipEventRecord(t1.e, 0));
+    HIP_CHECK(hipEventSynchronize(t1.e));
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventElapsedTime(&ms, t0.e, t1.e));
+  }
+  GemmResult r;
+  r.tflops = 2.0 * p.M * p.N * p.K * iters / (ms * 1e-3) / 1e12;
+  for (int t = 0; t < 256; ++t) {
+    int i = static_cast<int>((static_cast<int64_t>(t) * 1031 + 17) % p.M);
+    int j = static_cast<int>((static_cast<int64_t>(t) * 2053 + 29) % p.N);
+    float got = 0;
+    HIP_CHECK(hipMemcpy(&got, p.dc.template as<float>() + static_cast<size_t>(i) * p.Np + j,
+                        sizeof(float), hipMemcpyDeviceToHost));
+    note_err(r.max_err, err(got, i, j, p.K));
+  }
+  return r;
 }
 
 }  // namespace detail
@@ -256,10 +336,7 @@ inline void gemm_bf16(const float* a, const float* b, float* c, int M, int N,
   for (int k = 0; k < K; ++k)
     for (int j = 0; j < N; ++j)
       p.bt[j * p.Kp + k] = to_bf16_rne(b[static_cast<size_t>(k) * N + j]);
-  p.upload(device);
-  p.launch();
-  HIP_CHECK(hipGetLastError());
-  p.download(c);
+  detail::run_once(p, device, c);
 }
 
 // Self-contained exact check: integer pattern in [-4, 4], host reference in
@@ -268,19 +345,7 @@ inline double run_gemm_check(int M, int N, int K, int device = 0) {
   detail::require_exact_k(K, "run_gemm_check");
   detail::GemmProblem p(M, N, K);
   detail::fill_pattern(p);
-  p.upload(device);
-  p.launch();
-  HIP_CHECK(hipGetLastError());
-  std::vector<float> host(static_cast<size_t>(M) * N);
-  p.download(host.data());
-  double max_err = 0;
-  for (int i = 0; i < M; ++i)
-    for (int j = 0; j < N; ++j) {
-      double e = std::fabs(static_cast<double>(host[static_cast<size_t>(i) * N + j]) -
-                           static_cast<double>(detail::pattern_dot(i, j, K)));
-      detail::note_err(max_err, e);
-    }
-  return max_err;
+  return detail::run_full_check(p, device, detail::pattern_err);
 }
 
 // Timed run on the same integer pattern: one warm-up launch, `iters` launches
@@ -292,33 +357,8 @@ inline GemmResult run_gemm(int M = 4096, int N = 4096, int K = 1024,
   if (iters < 1) throw std::invalid_argument("run_gemm: iters must be >= 1");
   detail::GemmProblem p(M, N, K);
   detail::fill_pattern(p);
-  p.upload(device);
-  p.launch();  // warmup
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipDeviceSynchronize());
-  float ms = 0;
-  {
-    detail::Event t0, t1;
-    HIP_CHECK(hipEventRecord(t0.e, 0));
-    for (int i = 0; i < iters; ++i) p.launch();
-    HIP_CHECK(hipEventRecord(t1.e, 0));
-    HIP_CHECK(hipEventSynchronize(t1.e));
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventElapsedTime(&ms, t0.e, t1.e));
-  }
-  GemmResult r;
-  r.tflops = 2.0 * M * N * K * iters / (ms * 1e-3) / 1e12;
-  for (int t = 0; t < 256; ++t) {
-    int i = static_cast<int>((static_cast<int64_t>(t) * 1031 + 17) % M);
-    int j = static_cast<int>((static_cast<int64_t>(t) * 2053 + 29) % N);
-    float got = 0;
-    HIP_CHECK(hipMemcpy(&got, p.dc.as<float>() + static_cast<size_t>(i) * p.Np + j,
-                        sizeof(float), hipMemcpyDeviceToHost));
-    double e = std::fabs(static_cast<double>(got) -
-                         static_cast<double>(detail::pattern_dot(i, j, K)));
-    detail::note_err(r.max_err, e);
-  }
-  return r;
+  return detail::run_timed(p, iters, device, detail::pattern_err);
 }
 
 }  // namespace payload
+

@@ -144,6 +144,69 @@ static bool print_memcheck(const MemcheckResult& r) {
   return ok;
 }
 
+// the three GEMM payloads share their verbs' arguments and report lines
+struct GemmVerb {
+  const char* name;
+  GemmResult (*run)(int m, int n, int k, int iters, int device);
+  double (*check)(int m, int n, int k, int device);
+  int default_k;
+};
+
+static const GemmVerb kGemmVerbs[] = {
+    {"gemm", run_gemm, run_gemm_check, 1024},
+    {"mxgemm", run_mxgemm, run_mxgemm_check, 2048},
+    {"mx4gemm", run_mx4gemm, run_mx4gemm_check, 2048},
+};
+
+static const GemmVerb* find_gemm_verb(const char* name) {
+  for (const GemmVerb& g : kGemmVerbs)
+    if (std::strcmp(name, g.name) == 0) return &g;
+  return nullptr;
+}
+
+// <verb> [M N K [ITERS]]: the timed run
+static bool print_timed_gemm(const GemmVerb& g, int argc, char** argv) {
+  int m = argc > 4 ? std::atoi(argv[2]) : 4096;
+  int n = argc > 4 ? std::atoi(argv[3]) : 4096;
+  int k = argc > 4 ? std::atoi(argv[4]) : g.default_k;
+  int iters = argc > 5 ? std::atoi(argv[5]) : 10;
+  GemmResult r = g.run(m, n, k, iters, 0);
+  bool ok = r.max_err == 0.0;
+  std::printf(
+      "{\"ok\": %s, \"cmd\": \"%s\", \"m\": %d, \"n\": %d, \"k\": %d, "
+      "\"iters\": %d, \"tflops\": %.2f, \"max_err\": %g}\n",
+      ok ? "true" : "false", g.name, m, n, k, iters, r.tflops, json_num(r.max_err));
+  return ok;
+}
+
+// serve's <verb> [M N K]: the full check
+static void print_gemm_check(const GemmVerb& g, std::istringstream& iss) {
+  int m = 96, n = 160, k = 224, tm, tn, tk;
+  if (iss >> tm >> tn >> tk) { m = tm; n = tn; k = tk; }
+  double err = g.check(m, n, k, 0);
+  std::printf(
+      "{\"ok\": %s, \"cmd\": \"%s\", \"m\": %d, \"n\": %d, "
+      "\"k\": %d, \"max_err\": %g}\n",
+      err == 0.0 ? "true" : "false", g.name, m, n, k, json_num(err));
+}
+
+// one census run: the XCDs that ran a workgroup, and the per-XCD counts as the
+// elements of a JSON array
+struct Census {
+  std::vector<unsigned int> per_xcd = run_xcd_census();
+
+  int xcds() const {
+    int n = 0;
+    for (unsigned v : per_xcd)
+      if (v) ++n;
+    return n;
+  }
+
+  void print_per_xcd() const {
+    for (int i = 0; i < 8; ++i) std::printf("%s%u", i ? ", " : "", per_xcd[i]);
+  }
+};
+
 int main(int argc, char** argv) {
   const char* cmd = argc > 1 ? argv[1] : "info";
   try {
@@ -179,49 +242,12 @@ int main(int argc, char** argv) {
     } else if (std::strcmp(cmd, "busy") == 0) {
       print_busy(argc > 2 ? argv[2] : "100");
     } else if (std::strcmp(cmd, "census") == 0) {
-      auto c = run_xcd_census();
+      Census census;
       std::printf("{\"ok\": true, \"cmd\": \"census\", \"per_xcd\": [");
-      for (int i = 0; i < 8; ++i) std::printf("%s%u", i ? ", " : "", c[i]);
-      int xcds = 0;
-      for (unsigned v : c)
-        if (v) ++xcds;
-      std::printf("], \"xcds_visible\": %d}\n", xcds);
-    } else if (std::strcmp(cmd, "gemm") == 0) {
-      int m = argc > 4 ? std::atoi(argv[2]) : 4096;
-      int n = argc > 4 ? std::atoi(argv[3]) : 4096;
-      int k = argc > 4 ? std::atoi(argv[4]) : 1024;
-      int iters = argc > 5 ? std::atoi(argv[5]) : 10;
-      GemmResult r = run_gemm(m, n, k, iters);
-      bool ok = r.max_err == 0.0;
-      std::printf(
-          "{\"ok\": %s, \"cmd\": \"gemm\", \"m\": %d, \"n\": %d, \"k\": %d, "
-          "\"iters\": %d, \"tflops\": %.2f, \"max_err\": %g}\n",
-          ok ? "true" : "false", m, n, k, iters, r.tflops, json_num(r.max_err));
-      return ok ? 0 : 1;
-    } else if (std::strcmp(cmd, "mxgemm") == 0) {
-      int m = argc > 4 ? std::atoi(argv[2]) : 4096;
-      int n = argc > 4 ? std::atoi(argv[3]) : 4096;
-      int k = argc > 4 ? std::atoi(argv[4]) : 2048;
-      int iters = argc > 5 ? std::atoi(argv[5]) : 10;
-      GemmResult r = run_mxgemm(m, n, k, iters);
-      bool ok = r.max_err == 0.0;
-      std::printf(
-          "{\"ok\": %s, \"cmd\": \"mxgemm\", \"m\": %d, \"n\": %d, \"k\": %d, "
-          "\"iters\": %d, \"tflops\": %.2f, \"max_err\": %g}\n",
-          ok ? "true" : "false", m, n, k, iters, r.tflops, json_num(r.max_err));
-      return ok ? 0 : 1;
-    } else if (std::strcmp(cmd, "mx4gemm") == 0) {
-      int m = argc > 4 ? std::atoi(argv[2]) : 4096;
-      int n = argc > 4 ? std::atoi(argv[3]) : 4096;
-      int k = argc > 4 ? std::atoi(argv[4]) : 2048;
-      int iters = argc > 5 ? std::atoi(argv[5]) : 10;
-      GemmResult r = run_mx4gemm(m, n, k, iters);
-      bool ok = r.max_err == 0.0;
-      std::printf(
-          "{\"ok\": %s, \"cmd\": \"mx4gemm\", \"m\": %d, \"n\": %d, \"k\": %d, "
-          "\"iters\": %d, \"tflops\": %.2f, \"max_err\": %g}\n",
-          ok ? "true" : "false", m, n, k, iters, r.tflops, json_num(r.max_err));
-      return ok ? 0 : 1;
+      census.print_per_xcd();
+      std::printf("], \"xcds_visible\": %d}\n", census.xcds());
+    } else if (const GemmVerb* g = find_gemm_verb(cmd)) {
+      return print_timed_gemm(*g, argc, argv) ? 0 : 1;
     } else if (std::strcmp(cmd, "attn") == 0) {
       int b = argc > 5 ? std::atoi(argv[2]) : 32;
       int hq = argc > 5 ? std::atoi(argv[3]) : 64;
@@ -272,10 +298,8 @@ int main(int argc, char** argv) {
     } else if (std::strcmp(cmd, "verify") == 0) {
       int expected = argc > 2 ? std::atoi(argv[2]) : 0;
       DeviceInfo info = get_device_info(0);
-      auto census = run_xcd_census();
-      int xcds = 0;
-      for (unsigned v : census)
-        if (v) ++xcds;
+      Census census;
+      int xcds = census.xcds();
       double vecadd_err = run_vecadd(1 << 20);
       double gemm_err = run_gemm_check(96, 160, 224);
       MembwResult mb = run_membw_check(size_t{256} << 20, 5);
@@ -290,7 +314,7 @@ int main(int argc, char** argv) {
       std::printf("{\"ok\": %s, \"cmd\": \"verify\", \"xcds_expected\": %d, "
                   "\"xcds_visible\": %d, \"per_xcd\": [",
                   ok ? "true" : "false", expected, xcds);
-      for (int i = 0; i < 8; ++i) std::printf("%s%u", i ? ", " : "", census[i]);
+      census.print_per_xcd();
       int per = xcds > 0 ? xcds : 1;
       std::printf(
           "], \"cu_count\": %d, \"total_mem_gb\": %.1f, \"vecadd_max_err\": %g, "
@@ -325,30 +349,8 @@ int main(int argc, char** argv) {
             size_t n = 1 << 20;
             iss >> n;
             print_vecadd(n);
-          } else if (verb == "gemm") {
-            int m = 96, n = 160, k = 224, tm, tn, tk;
-            if (iss >> tm >> tn >> tk) { m = tm; n = tn; k = tk; }
-            double err = run_gemm_check(m, n, k);
-            std::printf(
-                "{\"ok\": %s, \"cmd\": \"gemm\", \"m\": %d, \"n\": %d, "
-                "\"k\": %d, \"max_err\": %g}\n",
-                err == 0.0 ? "true" : "false", m, n, k, json_num(err));
-          } else if (verb == "mxgemm") {
-            int m = 96, n = 160, k = 224, tm, tn, tk;
-            if (iss >> tm >> tn >> tk) { m = tm; n = tn; k = tk; }
-            double err = run_mxgemm_check(m, n, k);
-            std::printf(
-                "{\"ok\": %s, \"cmd\": \"mxgemm\", \"m\": %d, \"n\": %d, "
-                "\"k\": %d, \"max_err\": %g}\n",
-                err == 0.0 ? "true" : "false", m, n, k, json_num(err));
-          } else if (verb == "mx4gemm") {
-            int m = 96, n = 160, k = 224, tm, tn, tk;
-            if (iss >> tm >> tn >> tk) { m = tm; n = tn; k = tk; }
-            double err = run_mx4gemm_check(m, n, k);
-            std::printf(
-                "{\"ok\": %s, \"cmd\": \"mx4gemm\", \"m\": %d, \"n\": %d, "
-                "\"k\": %d, \"max_err\": %g}\n",
-                err == 0.0 ? "true" : "false", m, n, k, json_num(err));
+          } else if (const GemmVerb* g = find_gemm_verb(verb.c_str())) {
+            print_gemm_check(*g, iss);
           } else if (verb == "attn") {
             int b = 2, hq = 8, hkv = 2, len = 300, tb, tq, tk, tl;
             if (iss >> tb >> tq >> tk >> tl) { b = tb; hq = tq; hkv = tk; len = tl; }

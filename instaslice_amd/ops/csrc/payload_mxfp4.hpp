@@ -53,9 +53,9 @@
 // buffers for any shape.
 //
 // Included by payload_core.hpp after payload_mxgemm.hpp (needs mx_lds_off,
-// mx_scale_off, i32x4, i32x8, the kMx* constants, detail::mx_pat_sa/sb,
-// detail::mx_pattern_err, detail::require_exact_mx_k and what that header
-// needs).
+// mx_scale_off, i32x4, i32x8, the kMx* constants, detail::mx_block_scale and
+// the MX host layer that detail::Mxfp4 below parameterises: detail::MxProblem,
+// gemm_mx, gemm_mx_raw, run_mx_check and run_mx_timed).
 
 #pragma once
 
@@ -243,17 +243,7 @@ inline float from_e2m1(uint8_t code) {
 inline void mx4_quantize_row(const float* x, int K, uint8_t* codes, uint8_t* scales) {
   for (int k0 = 0; k0 < K; k0 += kMxBlock) {
     const int n = std::min(kMxBlock, K - k0);
-    float amax = 0.f;
-    for (int k = 0; k < n; ++k) {
-      float v = std::fabs(x[k0 + k]);
-      if (v > amax) amax = v;
-    }
-    int scale = 127;
-    if (amax > 0.f) {
-      // ilogb is floor(log2) for normals and subnormals; inf clamps to 254
-      long e = std::isinf(amax) ? 1000 : std::ilogb(amax);
-      scale = static_cast<int>(std::min(254l, std::max(0l, e - 2 + 127)));
-    }
+    const int scale = detail::mx_block_scale(x + k0, n, 2);
     scales[k0 / kMxBlock] = static_cast<uint8_t>(scale);
     // x * 2^(127 - scale) < 8 whenever the clamp at 0 is not hit, and a power
     // of two scaling is exact unless the result is an fp32 subnormal, which is
@@ -276,87 +266,23 @@ inline void pack_fp4(const uint8_t* codes, int K, uint8_t* out) {
 
 namespace detail {
 
-// Padded packed operands and scales on the host plus their device images and
-// the padded C. Size limits as MxProblem's.
-struct Mx4Problem {
-  int M, N, K;
-  size_t Mp, Np, Kp, Kbytes, Kb;  // Kbytes: bytes, Kb: scale bytes per padded row
-  std::vector<uint8_t> a, bt;     // Mp x Kbytes, Np x Kbytes, zero-padded
-  std::vector<uint8_t> sa, sbt;   // scale images (mx_scale_off), padded with 127
-  DeviceBuffer da, dbt, dsa, dsbt, dc;
-
-  Mx4Problem(int m, int n, int k) : M(m), N(n), K(k) {
-    if (m < 1 || n < 1 || k < 1)
-      throw std::invalid_argument("mx4gemm: M, N and K must be >= 1");
-    Mp = round_up(m, kMxBM);
-    Np = round_up(n, kMxBN);
-    Kp = round_up(k, kMx4BK);
-    if (Mp / kMxBM > 65535 || Np > 0x7FFFFF80u || Kp > (1u << 24))
-      throw std::invalid_argument("mx4gemm: shape too large");
-    Kbytes = Kp / 2;
-    Kb = Kp / kMxBlock;
-    a.assign(Mp * Kbytes, 0);
-    bt.assign(Np * Kbytes, 0);
-    sa.assign(Mp * Kb, 127);
-    sbt.assign(Np * Kb, 127);
+// the e2m1 format of detail::MxProblem (payload_mxgemm.hpp): packed operands,
+// K padded to 256; size limits as for e4m3
+struct Mxfp4 {
+  static constexpr const char* name = "mx4gemm";
+  static constexpr int kBK = kMx4BK;
+  static constexpr int kPerByte = 2;
+  static constexpr auto kernel = gemm_mxfp4_kernel;
+  static uint8_t encode(float f) { return to_e2m1_sat(f); }
+  static void quantize_row(const float* x, int K, uint8_t* codes, uint8_t* scales) {
+    mx4_quantize_row(x, K, codes, scales);
   }
-
-  // element k of row i of A / of column j of B
-  void set_a(size_t i, size_t k, uint8_t code) { put(a[i * Kbytes + k / 2], k, code); }
-  void set_b(size_t k, size_t j, uint8_t code) { put(bt[j * Kbytes + k / 2], k, code); }
-
-  void upload(int device) {
-    HIP_CHECK(hipSetDevice(device));
-    da.alloc(a.size());
-    dbt.alloc(bt.size());
-    dsa.alloc(sa.size());
-    dsbt.alloc(sbt.size());
-    dc.alloc(Mp * Np * sizeof(float));
-    HIP_CHECK(hipMemcpy(da.p, a.data(), a.size(), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dbt.p, bt.data(), bt.size(), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dsa.p, sa.data(), sa.size(), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dsbt.p, sbt.data(), sbt.size(), hipMemcpyHostToDevice));
-  }
-
-  void launch() const {
-    dim3 grid(static_cast<unsigned>(Np / kMxBN), static_cast<unsigned>(Mp / kMxBM));
-    hipLaunchKernelGGL(gemm_mxfp4_kernel, grid, dim3(kBlock), 0, 0,
-                       da.as<const uint8_t>(), dbt.as<const uint8_t>(),
-                       dsa.as<const uint8_t>(), dsbt.as<const uint8_t>(),
-                       dc.as<float>(), static_cast<int>(Np), static_cast<int>(Kp));
-  }
-
-  // the un-padded M x N region, row-major, into c
-  void download(float* c) const {
-    HIP_CHECK(hipMemcpy2D(c, static_cast<size_t>(N) * sizeof(float), dc.p,
-                          Np * sizeof(float), static_cast<size_t>(N) * sizeof(float),
-                          M, hipMemcpyDeviceToHost));
-  }
-
- private:
   static void put(uint8_t& byte, size_t k, uint8_t code) {
     byte = (k & 1) ? static_cast<uint8_t>((byte & 0x0F) | (code << 4))
                    : static_cast<uint8_t>((byte & 0xF0) | (code & 15));
   }
+  static void pack(const uint8_t* codes, int K, uint8_t* out) { pack_fp4(codes, K, out); }
 };
-
-// the MXFP8 integer pattern (gemm_pat_a / _b, mx_pat_sa / _sb) in e2m1: every
-// integer in [-4, 4] is an e2m1 value
-inline void fill_mx4_pattern(Mx4Problem& p) {
-  const int blocks = (p.K + kMxBlock - 1) / kMxBlock;
-  for (int i = 0; i < p.M; ++i) {
-    for (int k = 0; k < p.K; ++k)
-      p.set_a(i, k, to_e2m1_sat(static_cast<float>(gemm_pat_a(i, k))));
-    for (int kb = 0; kb < blocks; ++kb)
-      p.sa[mx_scale_off(i, kb, p.Kb)] = static_cast<uint8_t>(127 + mx_pat_sa(i, kb));
-  }
-  for (int j = 0; j < p.N; ++j) {
-    for (int k = 0; k < p.K; ++k)
-      p.set_b(k, j, to_e2m1_sat(static_cast<float>(gemm_pat_b(k, j))));
-    for (int kb = 0; kb < blocks; ++kb)
-      p.sbt[mx_scale_off(j, kb, p.Kb)] = static_cast<uint8_t>(127 + mx_pat_sb(kb, j));
-  }
-}
 
 }  // namespace detail
 
@@ -366,22 +292,8 @@ inline void fill_mx4_pattern(Mx4Problem& p) {
 inline void gemm_mxfp4_raw(const uint8_t* a_codes, const uint8_t* a_scales,
                            const uint8_t* b_codes, const uint8_t* b_scales,
                            float* c, int M, int N, int K, int device = 0) {
-  detail::Mx4Problem p(M, N, K);
-  const size_t blocks = (static_cast<size_t>(K) + kMxBlock - 1) / kMxBlock;
-  for (int i = 0; i < M; ++i) {
-    pack_fp4(a_codes + static_cast<size_t>(i) * K, K, &p.a[i * p.Kbytes]);
-    for (size_t kb = 0; kb < blocks; ++kb)
-      p.sa[mx_scale_off(i, kb, p.Kb)] = a_scales[static_cast<size_t>(i) * blocks + kb];
-  }
-  for (int k = 0; k < K; ++k)
-    for (int j = 0; j < N; ++j) p.set_b(k, j, b_codes[static_cast<size_t>(k) * N + j]);
-  for (size_t kb = 0; kb < blocks; ++kb)
-    for (int j = 0; j < N; ++j)
-      p.sbt[mx_scale_off(j, kb, p.Kb)] = b_scales[kb * N + j];
-  p.upload(device);
-  p.launch();
-  HIP_CHECK(hipGetLastError());
-  p.download(c);
+  detail::gemm_mx_raw<detail::Mxfp4>(a_codes, a_scales, b_codes, b_scales, c, M, N, K,
+                                     device);
 }
 
 // General entry: c[M,N] = mx4(a[M,K]) · mx4(b[K,N]), all row-major float. Rows
@@ -389,33 +301,7 @@ inline void gemm_mxfp4_raw(const uint8_t* a_codes, const uint8_t* a_scales,
 // std::invalid_argument on a non-finite input, before any device work.
 inline void gemm_mxfp4(const float* a, const float* b, float* c, int M, int N,
                        int K, int device = 0) {
-  detail::Mx4Problem p(M, N, K);
-  for (size_t i = 0, n = static_cast<size_t>(M) * K; i < n; ++i)
-    if (!std::isfinite(a[i]))
-      throw std::invalid_argument("gemm_mxfp4: a has a non-finite element");
-  for (size_t i = 0, n = static_cast<size_t>(K) * N; i < n; ++i)
-    if (!std::isfinite(b[i]))
-      throw std::invalid_argument("gemm_mxfp4: b has a non-finite element");
-  const size_t blocks = (static_cast<size_t>(K) + kMxBlock - 1) / kMxBlock;
-  std::vector<uint8_t> codes(K), scales(blocks);
-  for (int i = 0; i < M; ++i) {
-    mx4_quantize_row(a + static_cast<size_t>(i) * K, K, codes.data(), scales.data());
-    pack_fp4(codes.data(), K, &p.a[i * p.Kbytes]);
-    for (size_t kb = 0; kb < blocks; ++kb)
-      p.sa[mx_scale_off(i, kb, p.Kb)] = scales[kb];
-  }
-  std::vector<float> col(K);
-  for (int j = 0; j < N; ++j) {
-    for (int k = 0; k < K; ++k) col[k] = b[static_cast<size_t>(k) * N + j];
-    mx4_quantize_row(col.data(), K, codes.data(), scales.data());
-    pack_fp4(codes.data(), K, &p.bt[j * p.Kbytes]);
-    for (size_t kb = 0; kb < blocks; ++kb)
-      p.sbt[mx_scale_off(j, kb, p.Kb)] = scales[kb];
-  }
-  p.upload(device);
-  p.launch();
-  HIP_CHECK(hipGetLastError());
-  p.download(c);
+  detail::gemm_mx<detail::Mxfp4>("gemm_mxfp4", a, b, c, M, N, K, device);
 }
 
 // Self-contained exact check on the MXFP8 payload's pattern: integer elements
@@ -424,20 +310,7 @@ inline void gemm_mxfp4(const float* a, const float* b, float* c, int M, int N,
 // values and scales are the same numbers as there, so the exactness argument
 // at kMxMaxExactK and its limit K <= 2048 carry over unchanged.
 inline double run_mx4gemm_check(int M, int N, int K, int device = 0) {
-  detail::require_exact_mx_k(K, "run_mx4gemm_check");
-  detail::Mx4Problem p(M, N, K);
-  detail::fill_mx4_pattern(p);
-  p.upload(device);
-  p.launch();
-  HIP_CHECK(hipGetLastError());
-  std::vector<float> host(static_cast<size_t>(M) * N);
-  p.download(host.data());
-  double max_err = 0;
-  for (int i = 0; i < M; ++i)
-    for (int j = 0; j < N; ++j)
-      detail::note_err(max_err, detail::mx_pattern_err(
-                                    host[static_cast<size_t>(i) * N + j], i, j, K));
-  return max_err;
+  return detail::run_mx_check<detail::Mxfp4>("run_mx4gemm_check", M, N, K, device);
 }
 
 // Timed run on the same pattern, with run_mxgemm's defaults so that the two
@@ -446,35 +319,8 @@ inline double run_mx4gemm_check(int M, int N, int K, int device = 0) {
 // exactly. FLOPs are counted as 2 M N K.
 inline GemmResult run_mx4gemm(int M = 4096, int N = 4096, int K = 2048,
                               int iters = 10, int device = 0) {
-  detail::require_exact_mx_k(K, "run_mx4gemm");
-  if (iters < 1) throw std::invalid_argument("run_mx4gemm: iters must be >= 1");
-  detail::Mx4Problem p(M, N, K);
-  detail::fill_mx4_pattern(p);
-  p.upload(device);
-  p.launch();  // warmup
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipDeviceSynchronize());
-  float ms = 0;
-  {
-    detail::Event t0, t1;
-    HIP_CHECK(hipEventRecord(t0.e, 0));
-    for (int i = 0; i < iters; ++i) p.launch();
-    HIP_CHECK(hipEventRecord(t1.e, 0));
-    HIP_CHECK(hipEventSynchronize(t1.e));
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventElapsedTime(&ms, t0.e, t1.e));
-  }
-  GemmResult r;
-  r.tflops = 2.0 * M * N * K * iters / (ms * 1e-3) / 1e12;
-  for (int t = 0; t < 256; ++t) {
-    int i = static_cast<int>((static_cast<int64_t>(t) * 1031 + 17) % M);
-    int j = static_cast<int>((static_cast<int64_t>(t) * 2053 + 29) % N);
-    float got = 0;
-    HIP_CHECK(hipMemcpy(&got, p.dc.as<float>() + static_cast<size_t>(i) * p.Np + j,
-                        sizeof(float), hipMemcpyDeviceToHost));
-    detail::note_err(r.max_err, detail::mx_pattern_err(got, i, j, K));
-  }
-  return r;
+  return detail::run_mx_timed<detail::Mxfp4>("run_mx4gemm", M, N, K, iters, device);
 }
 
 }  // namespace payload
+

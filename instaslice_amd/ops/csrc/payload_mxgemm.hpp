@@ -49,8 +49,8 @@
 // the byte 127, not 0. Here the scales are always loaded values.
 //
 // Included by payload_core.hpp after payload_gemm.hpp (needs HIP_CHECK, kBlock,
-// f32x4, detail::DeviceBuffer, detail::Event, detail::round_up, gemm_pat_a/b and
-// detail::note_err).
+// f32x4, detail::DeviceBuffer, gemm_pat_a/b, and the shared GEMM host layer:
+// detail::GemmShape, run_once, run_full_check and run_timed).
 
 #pragma once
 
@@ -264,6 +264,25 @@ inline float from_e4m3(uint8_t code) {
   return (code & 0x80) ? -v : v;
 }
 
+namespace detail {
+
+// E8M0 scale byte of one MX block of n <= 32 floats for an element format
+// whose largest value has exponent emax: clamp(floor(log2(amax)) - emax + 127,
+// 0, 254); 127 for an all-zero block. A NaN element takes no part in amax.
+inline int mx_block_scale(const float* x, int n, int emax) {
+  float amax = 0.f;
+  for (int k = 0; k < n; ++k) {
+    float v = std::fabs(x[k]);
+    if (v > amax) amax = v;
+  }
+  if (!(amax > 0.f)) return 127;
+  // ilogb is floor(log2) for normals and subnormals; inf clamps to 254
+  long e = std::isinf(amax) ? 1000 : std::ilogb(amax);
+  return static_cast<int>(std::min(254l, std::max(0l, e - emax + 127)));
+}
+
+}  // namespace detail
+
 // OCP MX quantization of one row of K floats: per block of 32 elements (a last
 // partial block as if padded with zeros) one E8M0 scale byte
 // clamp(floor(log2(amax)) - 8 + 127, 0, 254), 8 being the exponent of the
@@ -273,17 +292,7 @@ inline float from_e4m3(uint8_t code) {
 inline void mx_quantize_row(const float* x, int K, uint8_t* codes, uint8_t* scales) {
   for (int k0 = 0; k0 < K; k0 += kMxBlock) {
     const int n = std::min(kMxBlock, K - k0);
-    float amax = 0.f;
-    for (int k = 0; k < n; ++k) {
-      float v = std::fabs(x[k0 + k]);
-      if (v > amax) amax = v;
-    }
-    int scale = 127;
-    if (amax > 0.f) {
-      // ilogb is floor(log2) for normals and subnormals; inf clamps to 254
-      long e = std::isinf(amax) ? 1000 : std::ilogb(amax);
-      scale = static_cast<int>(std::min(254l, std::max(0l, e - 8 + 127)));
-    }
+    const int scale = detail::mx_block_scale(x + k0, n, 8);
     scales[k0 / kMxBlock] = static_cast<uint8_t>(scale);
     // |127 - scale| <= 127 and x * 2^(127 - scale) < 2^9 whenever the clamp at
     // 0 is not hit, so the scaling is exact unless the result is an fp32
@@ -297,29 +306,55 @@ inline void mx_quantize_row(const float* x, int K, uint8_t* codes, uint8_t* scal
 
 namespace detail {
 
-// Padded operands and scales on the host plus their device images and the
-// padded C.
-struct MxProblem {
-  int M, N, K;
-  size_t Mp, Np, Kp, Kb;     // Kb: scale bytes per padded row
-  std::vector<uint8_t> a, bt;    // Mp x Kp, Np x Kp, zero-padded
-  std::vector<uint8_t> sa, sbt;  // scale images (mx_scale_off), padded with 127
-  DeviceBuffer da, dbt, dsa, dsbt, dc;
+static_assert(kMxBM == kGemmBM && kMxBN == kGemmBN, "GemmShape pads M and N");
 
-  MxProblem(int m, int n, int k) : M(m), N(n), K(k) {
-    if (m < 1 || n < 1 || k < 1)
-      throw std::invalid_argument("mxgemm: M, N and K must be >= 1");
-    Mp = round_up(m, kMxBM);
-    Np = round_up(n, kMxBN);
-    Kp = round_up(k, kMxBK);
-    if (Mp / kMxBM > 65535 || Np > 0x7FFFFF80u || Kp > (1u << 24))
-      throw std::invalid_argument("mxgemm: shape too large");
+// What tells the MX formats apart on the host. A format F has
+//   name          the payload's name in messages
+//   kBK           the kernel's K-step, in elements
+//   kPerByte      elements per byte of the device image
+//   kernel        the GEMM kernel (gemm_mxfp8_kernel's signature)
+//   encode        float -> element code, one per byte
+//   quantize_row  the format's mx*_quantize_row
+//   put           the code of element k into its byte of the image
+//   pack          a row of K codes, one per byte, into its image bytes
+struct Mxfp8 {
+  static constexpr const char* name = "mxgemm";
+  static constexpr int kBK = kMxBK;
+  static constexpr int kPerByte = 1;
+  static constexpr auto kernel = gemm_mxfp8_kernel;
+  static uint8_t encode(float f) { return to_e4m3_sat(f); }
+  static void quantize_row(const float* x, int K, uint8_t* codes, uint8_t* scales) {
+    mx_quantize_row(x, K, codes, scales);
+  }
+  static void put(uint8_t& byte, size_t, uint8_t code) { byte = code; }
+  static void pack(const uint8_t* codes, int K, uint8_t* out) {
+    std::memcpy(out, codes, K);
+  }
+};
+
+// Padded operands and scales of format F on the host plus their device images.
+template <class F>
+struct MxProblem : GemmShape {
+  size_t Kbytes, Kb;             // per padded row: operand bytes, scale bytes
+  std::vector<uint8_t> a, bt;    // Mp x Kbytes, Np x Kbytes, zero-padded
+  std::vector<uint8_t> sa, sbt;  // scale images (mx_scale_off), padded with 127
+  DeviceBuffer da, dbt, dsa, dsbt;
+
+  MxProblem(int m, int n, int k) : GemmShape(F::name, m, n, k, F::kBK, 1u << 24) {
+    Kbytes = Kp / F::kPerByte;
     Kb = Kp / kMxBlock;
-    a.assign(Mp * Kp, 0);
-    bt.assign(Np * Kp, 0);
+    a.assign(Mp * Kbytes, 0);
+    bt.assign(Np * Kbytes, 0);
     sa.assign(Mp * Kb, 127);
     sbt.assign(Np * Kb, 127);
   }
+
+  uint8_t* row_a(size_t i) { return &a[i * Kbytes]; }
+  uint8_t* row_bt(size_t j) { return &bt[j * Kbytes]; }
+
+  // element k of row i of A / of column j of B
+  void set_a(size_t i, size_t k, uint8_t code) { F::put(row_a(i)[k / F::kPerByte], k, code); }
+  void set_b(size_t k, size_t j, uint8_t code) { F::put(row_bt(j)[k / F::kPerByte], k, code); }
 
   void upload(int device) {
     HIP_CHECK(hipSetDevice(device));
@@ -335,20 +370,20 @@ struct MxProblem {
   }
 
   void launch() const {
-    dim3 grid(static_cast<unsigned>(Np / kMxBN), static_cast<unsigned>(Mp / kMxBM));
-    hipLaunchKernelGGL(gemm_mxfp8_kernel, grid, dim3(kBlock), 0, 0,
+    hipLaunchKernelGGL(F::kernel, grid(), dim3(kBlock), 0, 0,
                        da.as<const uint8_t>(), dbt.as<const uint8_t>(),
                        dsa.as<const uint8_t>(), dsbt.as<const uint8_t>(),
                        dc.as<float>(), static_cast<int>(Np), static_cast<int>(Kp));
   }
-
-  // the un-padded M x N region, row-major, into c
-  void download(float* c) const {
-    HIP_CHECK(hipMemcpy2D(c, static_cast<size_t>(N) * sizeof(float), dc.p,
-                          Np * sizeof(float), static_cast<size_t>(N) * sizeof(float),
-                          M, hipMemcpyDeviceToHost));
-  }
 };
+
+// the `blocks` scales of row `row` of A (or column `row` of B), `stride` bytes
+// apart at `scales`, into their places in a scale image of Kb blocks per row
+inline void scatter_scales(std::vector<uint8_t>& image, size_t row, size_t Kb,
+                           const uint8_t* scales, size_t blocks, size_t stride = 1) {
+  for (size_t kb = 0; kb < blocks; ++kb)
+    image[mx_scale_off(row, kb, Kb)] = scales[kb * stride];
+}
 
 // scale exponents of the exact pattern, in [-2, 2]: asymmetric, and a
 // different function of (row, block) than of (block, column)
@@ -359,17 +394,20 @@ inline int mx_pat_sb(int kb, int j) {
   return static_cast<int>((2ll * kb + 3ll * j + 1) % 5) - 2;
 }
 
-inline void fill_mx_pattern(MxProblem& p) {
+// the gemm integer pattern (gemm_pat_a / _b: every integer in [-4, 4] is an
+// e4m3 and an e2m1 value) with the scale pattern above
+template <class F>
+void fill_mx_pattern(MxProblem<F>& p) {
   const int blocks = (p.K + kMxBlock - 1) / kMxBlock;
   for (int i = 0; i < p.M; ++i) {
     for (int k = 0; k < p.K; ++k)
-      p.a[i * p.Kp + k] = to_e4m3_sat(static_cast<float>(gemm_pat_a(i, k)));
+      p.set_a(i, k, F::encode(static_cast<float>(gemm_pat_a(i, k))));
     for (int kb = 0; kb < blocks; ++kb)
       p.sa[mx_scale_off(i, kb, p.Kb)] = static_cast<uint8_t>(127 + mx_pat_sa(i, kb));
   }
   for (int j = 0; j < p.N; ++j) {
     for (int k = 0; k < p.K; ++k)
-      p.bt[j * p.Kp + k] = to_e4m3_sat(static_cast<float>(gemm_pat_b(k, j)));
+      p.set_b(k, j, F::encode(static_cast<float>(gemm_pat_b(k, j))));
     for (int kb = 0; kb < blocks; ++kb)
       p.sbt[mx_scale_off(j, kb, p.Kb)] = static_cast<uint8_t>(127 + mx_pat_sb(kb, j));
   }
@@ -398,6 +436,70 @@ inline void require_exact_mx_k(int k, const char* who) {
                                 "only up to there)");
 }
 
+// the raw entry of format F: codes one per byte, row-major as given
+template <class F>
+void gemm_mx_raw(const uint8_t* a_codes, const uint8_t* a_scales,
+                 const uint8_t* b_codes, const uint8_t* b_scales, float* c, int M,
+                 int N, int K, int device) {
+  MxProblem<F> p(M, N, K);
+  const size_t blocks = (static_cast<size_t>(K) + kMxBlock - 1) / kMxBlock;
+  for (int i = 0; i < M; ++i) {
+    F::pack(a_codes + static_cast<size_t>(i) * K, K, p.row_a(i));
+    scatter_scales(p.sa, i, p.Kb, a_scales + static_cast<size_t>(i) * blocks, blocks);
+  }
+  for (int k = 0; k < K; ++k)
+    for (int j = 0; j < N; ++j) p.set_b(k, j, b_codes[static_cast<size_t>(k) * N + j]);
+  for (int j = 0; j < N; ++j)
+    scatter_scales(p.sbt, j, p.Kb, b_scales + j, blocks, N);
+  run_once(p, device, c);
+}
+
+// the general entry of format F; who names the public entry in messages
+template <class F>
+void gemm_mx(const char* who, const float* a, const float* b, float* c, int M, int N,
+             int K, int device) {
+  MxProblem<F> p(M, N, K);
+  for (size_t i = 0, n = static_cast<size_t>(M) * K; i < n; ++i)
+    if (!std::isfinite(a[i]))
+      throw std::invalid_argument(std::string(who) + ": a has a non-finite element");
+  for (size_t i = 0, n = static_cast<size_t>(K) * N; i < n; ++i)
+    if (!std::isfinite(b[i]))
+      throw std::invalid_argument(std::string(who) + ": b has a non-finite element");
+  const size_t blocks = (static_cast<size_t>(K) + kMxBlock - 1) / kMxBlock;
+  std::vector<uint8_t> codes(K), scales(blocks);
+  for (int i = 0; i < M; ++i) {
+    F::quantize_row(a + static_cast<size_t>(i) * K, K, codes.data(), scales.data());
+    F::pack(codes.data(), K, p.row_a(i));
+    scatter_scales(p.sa, i, p.Kb, scales.data(), blocks);
+  }
+  std::vector<float> col(K);
+  for (int j = 0; j < N; ++j) {
+    for (int k = 0; k < K; ++k) col[k] = b[static_cast<size_t>(k) * N + j];
+    F::quantize_row(col.data(), K, codes.data(), scales.data());
+    F::pack(codes.data(), K, p.row_bt(j));
+    scatter_scales(p.sbt, j, p.Kb, scales.data(), blocks);
+  }
+  run_once(p, device, c);
+}
+
+// the exact check and the timed run of format F on the scaled integer pattern
+template <class F>
+double run_mx_check(const char* who, int M, int N, int K, int device) {
+  require_exact_mx_k(K, who);
+  MxProblem<F> p(M, N, K);
+  fill_mx_pattern(p);
+  return run_full_check(p, device, mx_pattern_err);
+}
+
+template <class F>
+GemmResult run_mx_timed(const char* who, int M, int N, int K, int iters, int device) {
+  require_exact_mx_k(K, who);
+  if (iters < 1) throw std::invalid_argument(std::string(who) + ": iters must be >= 1");
+  MxProblem<F> p(M, N, K);
+  fill_mx_pattern(p);
+  return run_timed(p, iters, device, mx_pattern_err);
+}
+
 }  // namespace detail
 
 // Raw entry: operands already quantized. a_codes M x K, a_scales M x
@@ -406,23 +508,8 @@ inline void require_exact_mx_k(int k, const char* who) {
 inline void gemm_mxfp8_raw(const uint8_t* a_codes, const uint8_t* a_scales,
                            const uint8_t* b_codes, const uint8_t* b_scales,
                            float* c, int M, int N, int K, int device = 0) {
-  detail::MxProblem p(M, N, K);
-  const size_t blocks = (static_cast<size_t>(K) + kMxBlock - 1) / kMxBlock;
-  for (int i = 0; i < M; ++i) {
-    std::memcpy(&p.a[i * p.Kp], a_codes + static_cast<size_t>(i) * K, K);
-    for (size_t kb = 0; kb < blocks; ++kb)
-      p.sa[mx_scale_off(i, kb, p.Kb)] = a_scales[static_cast<size_t>(i) * blocks + kb];
-  }
-  for (int k = 0; k < K; ++k)
-    for (int j = 0; j < N; ++j)
-      p.bt[j * p.Kp + k] = b_codes[static_cast<size_t>(k) * N + j];
-  for (size_t kb = 0; kb < blocks; ++kb)
-    for (int j = 0; j < N; ++j)
-      p.sbt[mx_scale_off(j, kb, p.Kb)] = b_scales[kb * N + j];
-  p.upload(device);
-  p.launch();
-  HIP_CHECK(hipGetLastError());
-  p.download(c);
+  detail::gemm_mx_raw<detail::Mxfp8>(a_codes, a_scales, b_codes, b_scales, c, M, N, K,
+                                     device);
 }
 
 // General entry: c[M,N] = mx(a[M,K]) · mx(b[K,N]), all row-major float. Rows
@@ -430,51 +517,14 @@ inline void gemm_mxfp8_raw(const uint8_t* a_codes, const uint8_t* a_scales,
 // std::invalid_argument on a non-finite input, before any device work.
 inline void gemm_mxfp8(const float* a, const float* b, float* c, int M, int N,
                        int K, int device = 0) {
-  detail::MxProblem p(M, N, K);
-  for (size_t i = 0, n = static_cast<size_t>(M) * K; i < n; ++i)
-    if (!std::isfinite(a[i]))
-      throw std::invalid_argument("gemm_mxfp8: a has a non-finite element");
-  for (size_t i = 0, n = static_cast<size_t>(K) * N; i < n; ++i)
-    if (!std::isfinite(b[i]))
-      throw std::invalid_argument("gemm_mxfp8: b has a non-finite element");
-  const size_t blocks = (static_cast<size_t>(K) + kMxBlock - 1) / kMxBlock;
-  std::vector<uint8_t> scales(blocks);
-  for (int i = 0; i < M; ++i) {
-    mx_quantize_row(a + static_cast<size_t>(i) * K, K, &p.a[i * p.Kp], scales.data());
-    for (size_t kb = 0; kb < blocks; ++kb)
-      p.sa[mx_scale_off(i, kb, p.Kb)] = scales[kb];
-  }
-  std::vector<float> col(K);
-  for (int j = 0; j < N; ++j) {
-    for (int k = 0; k < K; ++k) col[k] = b[static_cast<size_t>(k) * N + j];
-    mx_quantize_row(col.data(), K, &p.bt[j * p.Kp], scales.data());
-    for (size_t kb = 0; kb < blocks; ++kb)
-      p.sbt[mx_scale_off(j, kb, p.Kb)] = scales[kb];
-  }
-  p.upload(device);
-  p.launch();
-  HIP_CHECK(hipGetLastError());
-  p.download(c);
+  detail::gemm_mx<detail::Mxfp8>("gemm_mxfp8", a, b, c, M, N, K, device);
 }
 
 // Self-contained exact check: integer elements in [-4, 4] (gemm_pat_a / _b),
 // scale exponents in [-2, 2] (mx_pat_sa / _sb), host reference in int64 in
 // units of 2^-4; returns max |C - ref| over the whole M x N result (expect 0.0).
 inline double run_mxgemm_check(int M, int N, int K, int device = 0) {
-  detail::require_exact_mx_k(K, "run_mxgemm_check");
-  detail::MxProblem p(M, N, K);
-  detail::fill_mx_pattern(p);
-  p.upload(device);
-  p.launch();
-  HIP_CHECK(hipGetLastError());
-  std::vector<float> host(static_cast<size_t>(M) * N);
-  p.download(host.data());
-  double max_err = 0;
-  for (int i = 0; i < M; ++i)
-    for (int j = 0; j < N; ++j)
-      detail::note_err(max_err, detail::mx_pattern_err(
-                                    host[static_cast<size_t>(i) * N + j], i, j, K));
-  return max_err;
+  return detail::run_mx_check<detail::Mxfp8>("run_mxgemm_check", M, N, K, device);
 }
 
 // Timed run on the same pattern: one warm-up launch, `iters` launches between
@@ -482,35 +532,8 @@ inline double run_mxgemm_check(int M, int N, int K, int device = 0) {
 // exactly. FLOPs are counted as 2 M N K.
 inline GemmResult run_mxgemm(int M = 4096, int N = 4096, int K = 2048,
                              int iters = 10, int device = 0) {
-  detail::require_exact_mx_k(K, "run_mxgemm");
-  if (iters < 1) throw std::invalid_argument("run_mxgemm: iters must be >= 1");
-  detail::MxProblem p(M, N, K);
-  detail::fill_mx_pattern(p);
-  p.upload(device);
-  p.launch();  // warmup
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipDeviceSynchronize());
-  float ms = 0;
-  {
-    detail::Event t0, t1;
-    HIP_CHECK(hipEventRecord(t0.e, 0));
-    for (int i = 0; i < iters; ++i) p.launch();
-    HIP_CHECK(hipEventRecord(t1.e, 0));
-    HIP_CHECK(hipEventSynchronize(t1.e));
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventElapsedTime(&ms, t0.e, t1.e));
-  }
-  GemmResult r;
-  r.tflops = 2.0 * M * N * K * iters / (ms * 1e-3) / 1e12;
-  for (int t = 0; t < 256; ++t) {
-    int i = static_cast<int>((static_cast<int64_t>(t) * 1031 + 17) % M);
-    int j = static_cast<int>((static_cast<int64_t>(t) * 2053 + 29) % N);
-    float got = 0;
-    HIP_CHECK(hipMemcpy(&got, p.dc.as<float>() + static_cast<size_t>(i) * p.Np + j,
-                        sizeof(float), hipMemcpyDeviceToHost));
-    detail::note_err(r.max_err, detail::mx_pattern_err(got, i, j, K));
-  }
-  return r;
+  return detail::run_mx_timed<detail::Mxfp8>("run_mxgemm", M, N, K, iters, device);
 }
 
 }  // namespace payload
+

@@ -7,10 +7,209 @@
 #include <pybind11/stl.h>
 
 #include <array>
+#include <tuple>
 
 #include "payload_core.hpp"
 
 namespace py = pybind11;
+
+namespace {
+
+// float32 arrays convert through forcecast | c_style: a non-contiguous or
+// other-dtype array is copied into a contiguous float32 one, and anything
+// that cannot be converted is a TypeError
+template <class T>
+using c_array = py::array_t<T, py::array::c_style | py::array::forcecast>;
+using f32_array = c_array<float>;
+using u32_array = c_array<uint32_t>;
+using u8_array = c_array<uint8_t>;
+
+// out[i] = f(x[i]): an array of x's shape, any rank
+template <class Out, class In>
+py::array_t<Out> map_elements(const c_array<In>& x, Out (*f)(In)) {
+  py::array_t<Out> out(std::vector<py::ssize_t>(x.shape(), x.shape() + x.ndim()));
+  const In* src = x.data();
+  Out* dst = out.mutable_data();
+  for (py::ssize_t i = 0, n = x.size(); i < n; ++i) dst[i] = f(src[i]);
+  return out;
+}
+
+// K, the length of the rows of x along its last axis, or ValueError; `what`
+// is the argument's name in the message
+int last_axis(const char* who, const char* what, const py::array& x) {
+  if (x.ndim() < 1)
+    throw py::value_error(std::string(who) + ": " + what +
+                          " must have at least one axis");
+  if (x.shape(x.ndim() - 1) < 1 || x.shape(x.ndim() - 1) > INT32_MAX)
+    throw py::value_error(std::string(who) + ": bad length of the last axis");
+  return static_cast<int>(x.shape(x.ndim() - 1));
+}
+
+// out[..., :] = row(x[..., :]) along the last axis: one uint8 array per width
+// in `widths`, shaped like x but that long in the last axis; row(src, dst...)
+// is called once per row of K elements with the row's place in each output
+template <class In, class... Width, class Row>
+auto map_rows(const c_array<In>& x, int K, Row row, Width... widths) {
+  std::vector<py::ssize_t> shape(x.shape(), x.shape() + x.ndim());
+  auto like = [&shape](py::ssize_t width) {
+    shape.back() = width;
+    return py::array_t<uint8_t>(shape);
+  };
+  std::tuple outs{like(widths)...};
+  const In* src = x.data();
+  for (py::ssize_t r = 0, rows = x.size() / K; r < rows; ++r)
+    std::apply(
+        [&](auto&... out) {
+          row(src + r * K, K, (out.mutable_data() + r * out.shape(out.ndim() - 1))...);
+        },
+        outs);
+  return outs;
+}
+
+void no_nan(const char* who, const f32_array& x) {
+  const float* src = x.data();
+  for (py::ssize_t i = 0, n = x.size(); i < n; ++i)
+    if (std::isnan(src[i]))
+      throw py::value_error(std::string(who) + ": x has a NaN element (e2m1 has no NaN)");
+}
+
+void e2m1_codes(const char* who, const u8_array& codes) {
+  const uint8_t* src = codes.data();
+  for (py::ssize_t i = 0, n = codes.size(); i < n; ++i)
+    if (src[i] > 15)
+      throw py::value_error(std::string(who) + ": an e2m1 code must be in 0 .. 15");
+}
+
+void any_code(const char*, const u8_array&) {}  // every byte is an e4m3 code
+
+// (codes uint8 [..., K], scales uint8 [..., ceil(K/32)]) of one of the MX
+// quantizers along the last axis
+using QuantizeRow = void (*)(const float*, int, uint8_t*, uint8_t*);
+auto quantize_rows(const f32_array& x, int K, QuantizeRow quantize) {
+  const py::ssize_t blocks = (K + payload::kMxBlock - 1) / payload::kMxBlock;
+  auto [codes, scales] = map_rows(x, K, quantize, py::ssize_t{K}, blocks);
+  return py::make_tuple(codes, scales);
+}
+
+// (M, N, K) of an (M,K) x (K,N) product, or ValueError
+std::array<int, 3> gemm_dims(const char* who, const py::array& a, const py::array& b) {
+  std::string w(who);
+  if (a.ndim() != 2 || b.ndim() != 2)
+    throw py::value_error(w + ": a and b must be 2-D");
+  if (a.shape(1) != b.shape(0))
+    throw py::value_error(w + ": a is (M,K) and b is (K,N): K differs");
+  if (a.shape(0) < 1 || a.shape(1) < 1 || b.shape(1) < 1)
+    throw py::value_error(w + ": empty operand");
+  if (a.shape(0) > INT32_MAX || a.shape(1) > INT32_MAX || b.shape(1) > INT32_MAX)
+    throw py::value_error(w + ": shape too large");
+  return std::array<int, 3>{static_cast<int>(a.shape(0)),
+                            static_cast<int>(b.shape(1)),
+                            static_cast<int>(a.shape(1))};
+}
+
+// C (M,N) of one of the general GEMM entries on float operands
+using GemmEntry = void (*)(const float*, const float*, float*, int, int, int, int);
+py::array_t<float> gemm_f32(const char* who, GemmEntry entry, const f32_array& a,
+                            const f32_array& b, int device) {
+  auto [M, N, K] = gemm_dims(who, a, b);
+  py::array_t<float> c({static_cast<py::ssize_t>(M), static_cast<py::ssize_t>(N)});
+  const float* pa = a.data();
+  const float* pb = b.data();
+  float* pc = c.mutable_data();
+  {
+    py::gil_scoped_release rel;
+    entry(pa, pb, pc, M, N, K, device);
+  }
+  return c;
+}
+
+// C (M,N) of one of the raw MX GEMM entries; check_codes rejects what is no
+// code of the entry's element format
+using GemmRawEntry = void (*)(const uint8_t*, const uint8_t*, const uint8_t*,
+                              const uint8_t*, float*, int, int, int, int);
+py::array_t<float> gemm_raw(const char* who, GemmRawEntry entry,
+                            void (*check_codes)(const char*, const u8_array&),
+                            const u8_array& a_codes, const u8_array& a_scales,
+                            const u8_array& b_codes, const u8_array& b_scales,
+                            int device) {
+  std::string w(who);
+  auto [M, N, K] = gemm_dims(who, a_codes, b_codes);
+  const py::ssize_t blocks = (K + payload::kMxBlock - 1) / payload::kMxBlock;
+  if (a_scales.ndim() != 2 || a_scales.shape(0) != M || a_scales.shape(1) != blocks)
+    throw py::value_error(w + ": a_scales must be (M, ceil(K/32))");
+  if (b_scales.ndim() != 2 || b_scales.shape(0) != blocks || b_scales.shape(1) != N)
+    throw py::value_error(w + ": b_scales must be (ceil(K/32), N)");
+  check_codes(who, a_codes);
+  check_codes(who, b_codes);
+  py::array_t<float> c({static_cast<py::ssize_t>(M), static_cast<py::ssize_t>(N)});
+  const uint8_t* pa = a_codes.data();
+  const uint8_t* psa = a_scales.data();
+  const uint8_t* pb = b_codes.data();
+  const uint8_t* psb = b_scales.data();
+  float* pc = c.mutable_data();
+  {
+    py::gil_scoped_release rel;
+    entry(pa, psa, pb, psb, pc, M, N, K, device);
+  }
+  return c;
+}
+
+// the report of one of the timed GEMM runs
+using TimedGemm = payload::GemmResult (*)(int, int, int, int, int);
+py::dict run_timed_gemm(TimedGemm run, int mm, int n, int k, int iters, int device) {
+  payload::GemmResult r;
+  {
+    py::gil_scoped_release rel;
+    r = run(mm, n, k, iters, device);
+  }
+  py::dict d;
+  d["m"] = mm;
+  d["n"] = n;
+  d["k"] = k;
+  d["iters"] = iters;
+  d["tflops"] = r.tflops;
+  d["max_err"] = r.max_err;
+  return d;
+}
+
+// the attention entries' q, k and v: q of rank q_rank (q_form in the message),
+// k and v (B,Hkv,L,128) and alike, head dim 128, one batch; or ValueError
+void attn_operands(const char* who, const f32_array& q, int q_rank, const char* q_form,
+                   const f32_array& k, const f32_array& v) {
+  std::string w(who);
+  if (q.ndim() != q_rank) throw py::value_error(w + ": q must be " + q_form);
+  if (k.ndim() != 4 || v.ndim() != 4)
+    throw py::value_error(w + ": k and v must be (B,Hkv,L,128)");
+  if (q.shape(q_rank - 1) != payload::kAttnD || k.shape(3) != payload::kAttnD)
+    throw py::value_error(w + ": head dim must be 128");
+  for (int i = 0; i < 4; ++i)
+    if (k.shape(i) != v.shape(i)) throw py::value_error(w + ": k and v differ in shape");
+  if (k.shape(0) != q.shape(0)) throw py::value_error(w + ": q and k differ in batch");
+}
+
+// scale=None is 1/sqrt(128); ValueError on a scale that is not finite
+float attn_scale(const char* who, const py::object& scale) {
+  if (scale.is_none()) return 1.0f / std::sqrt(static_cast<float>(payload::kAttnD));
+  float sc = scale.cast<float>();
+  if (!std::isfinite(sc)) throw py::value_error(std::string(who) + ": scale not finite");
+  return sc;
+}
+
+// ValueError unless every element of q, k and v is finite
+void attn_finite(const char* who, const f32_array& q, const f32_array& k,
+                 const f32_array& v) {
+  const float* pq = q.data();
+  const float* pk = k.data();
+  const float* pv = v.data();
+  for (py::ssize_t i = 0, n = q.size(); i < n; ++i)
+    if (!std::isfinite(pq[i]))
+      throw py::value_error(std::string(who) + ": q has a non-finite element");
+  for (py::ssize_t i = 0, n = k.size(); i < n; ++i)
+    if (!std::isfinite(pk[i]) || !std::isfinite(pv[i]))
+      throw py::value_error(std::string(who) + ": k or v has a non-finite element");
+}
+
+}  // namespace
 
 PYBIND11_MODULE(_payload, m) {
   m.doc() = "gfx950 HIP payload kernels (vecadd / membw / busy / xcd census / gemm / "
@@ -111,12 +310,6 @@ PYBIND11_MODULE(_payload, m) {
       },
       py::arg("device") = 0);
 
-  // float32 arrays convert through forcecast | c_style: a non-contiguous or
-  // other-dtype array is copied into a contiguous float32 one, and anything
-  // that cannot be converted is a TypeError
-  using f32_array = py::array_t<float, py::array::c_style | py::array::forcecast>;
-  using u32_array = py::array_t<uint32_t, py::array::c_style | py::array::forcecast>;
-
   m.def(
       "vecadd",
       [](f32_array a, f32_array b, int device, int blocks) {
@@ -169,41 +362,14 @@ PYBIND11_MODULE(_payload, m) {
 
   m.def(
       "to_bf16",
-      [](f32_array x) {
-        py::array_t<uint16_t> out(
-            std::vector<py::ssize_t>(x.shape(), x.shape() + x.ndim()));
-        const float* src = x.data();
-        uint16_t* dst = out.mutable_data();
-        for (py::ssize_t i = 0, n = x.size(); i < n; ++i)
-          dst[i] = payload::to_bf16_rne(src[i]);
-        return out;
-      },
+      [](f32_array x) { return map_elements(x, payload::to_bf16_rne); },
       py::arg("x"),
       "float32 -> bf16 bits (uint16), round-to-nearest-even; host only, no GPU");
 
   m.def(
       "gemm_bf16",
       [](f32_array a, f32_array b, int device) {
-        if (a.ndim() != 2 || b.ndim() != 2)
-          throw py::value_error("gemm_bf16: a and b must be 2-D");
-        if (a.shape(1) != b.shape(0))
-          throw py::value_error("gemm_bf16: a is (M,K) and b is (K,N): K differs");
-        if (a.shape(0) < 1 || a.shape(1) < 1 || b.shape(1) < 1)
-          throw py::value_error("gemm_bf16: empty operand");
-        if (a.shape(0) > INT32_MAX || a.shape(1) > INT32_MAX ||
-            b.shape(1) > INT32_MAX)
-          throw py::value_error("gemm_bf16: shape too large");
-        int M = static_cast<int>(a.shape(0)), K = static_cast<int>(a.shape(1)),
-            N = static_cast<int>(b.shape(1));
-        py::array_t<float> c({static_cast<py::ssize_t>(M), static_cast<py::ssize_t>(N)});
-        const float* pa = a.data();
-        const float* pb = b.data();
-        float* pc = c.mutable_data();
-        {
-          py::gil_scoped_release rel;
-          payload::gemm_bf16(pa, pb, pc, M, N, K, device);
-        }
-        return c;
+        return gemm_f32("gemm_bf16", payload::gemm_bf16, a, b, device);
       },
       py::arg("a"), py::arg("b"), py::arg("device") = 0,
       "C (M,N) float32 = bf16(a (M,K)) @ bf16(b (K,N)) on the MFMA kernel");
@@ -221,107 +387,38 @@ PYBIND11_MODULE(_payload, m) {
   m.def(
       "run_gemm",
       [](int mm, int n, int k, int iters, int device) {
-        payload::GemmResult r;
-        {
-          py::gil_scoped_release rel;
-          r = payload::run_gemm(mm, n, k, iters, device);
-        }
-        py::dict d;
-        d["m"] = mm;
-        d["n"] = n;
-        d["k"] = k;
-        d["iters"] = iters;
-        d["tflops"] = r.tflops;
-        d["max_err"] = r.max_err;
-        return d;
+        return run_timed_gemm(payload::run_gemm, mm, n, k, iters, device);
       },
       py::arg("m") = 4096, py::arg("n") = 4096, py::arg("k") = 1024,
       py::arg("iters") = 10, py::arg("device") = 0,
       "timed bf16 MFMA GEMM, 256 outputs spot-checked exactly; K <= 1024");
 
-  using u8_array = py::array_t<uint8_t, py::array::c_style | py::array::forcecast>;
-
   m.def(
       "to_e4m3",
-      [](f32_array x) {
-        py::array_t<uint8_t> out(
-            std::vector<py::ssize_t>(x.shape(), x.shape() + x.ndim()));
-        const float* src = x.data();
-        uint8_t* dst = out.mutable_data();
-        for (py::ssize_t i = 0, n = x.size(); i < n; ++i)
-          dst[i] = payload::to_e4m3_sat(src[i]);
-        return out;
-      },
+      [](f32_array x) { return map_elements(x, payload::to_e4m3_sat); },
       py::arg("x"),
       "float32 -> OCP e4m3fn byte (uint8), round-to-nearest-even, saturating at "
       "+-448; host only, no GPU");
 
   m.def(
       "from_e4m3",
-      [](u8_array codes) {
-        py::array_t<float> out(
-            std::vector<py::ssize_t>(codes.shape(), codes.shape() + codes.ndim()));
-        const uint8_t* src = codes.data();
-        float* dst = out.mutable_data();
-        for (py::ssize_t i = 0, n = codes.size(); i < n; ++i)
-          dst[i] = payload::from_e4m3(src[i]);
-        return out;
-      },
+      [](u8_array codes) { return map_elements(codes, payload::from_e4m3); },
       py::arg("codes"), "OCP e4m3fn byte (uint8) -> float32; host only, no GPU");
 
   m.def(
       "mx_quantize",
       [](f32_array x) {
-        if (x.ndim() < 1)
-          throw py::value_error("mx_quantize: x must have at least one axis");
-        if (x.shape(x.ndim() - 1) < 1 || x.shape(x.ndim() - 1) > INT32_MAX)
-          throw py::value_error("mx_quantize: bad length of the last axis");
-        const int K = static_cast<int>(x.shape(x.ndim() - 1));
-        const py::ssize_t blocks = (K + payload::kMxBlock - 1) / payload::kMxBlock;
-        std::vector<py::ssize_t> shape(x.shape(), x.shape() + x.ndim());
-        py::array_t<uint8_t> codes(shape);
-        shape.back() = blocks;
-        py::array_t<uint8_t> scales(shape);
-        const float* src = x.data();
-        uint8_t* pc = codes.mutable_data();
-        uint8_t* ps = scales.mutable_data();
-        for (py::ssize_t r = 0, rows = x.size() / K; r < rows; ++r)
-          payload::mx_quantize_row(src + r * K, K, pc + r * K, ps + r * blocks);
-        return py::make_tuple(codes, scales);
+        const int K = last_axis("mx_quantize", "x", x);
+        return quantize_rows(x, K, payload::mx_quantize_row);
       },
       py::arg("x"),
       "OCP MX quantization along the last axis: (codes uint8 [..., K], scales "
       "uint8 [..., ceil(K/32)]), e4m3 elements and E8M0 scales; host only, no GPU");
 
-  // (M, N, K) of an (M,K) x (K,N) product, or ValueError
-  auto mx_dims = [](const char* who, const py::array& a, const py::array& b) {
-    std::string w(who);
-    if (a.ndim() != 2 || b.ndim() != 2)
-      throw py::value_error(w + ": a and b must be 2-D");
-    if (a.shape(1) != b.shape(0))
-      throw py::value_error(w + ": a is (M,K) and b is (K,N): K differs");
-    if (a.shape(0) < 1 || a.shape(1) < 1 || b.shape(1) < 1)
-      throw py::value_error(w + ": empty operand");
-    if (a.shape(0) > INT32_MAX || a.shape(1) > INT32_MAX || b.shape(1) > INT32_MAX)
-      throw py::value_error(w + ": shape too large");
-    return std::array<int, 3>{static_cast<int>(a.shape(0)),
-                              static_cast<int>(b.shape(1)),
-                              static_cast<int>(a.shape(1))};
-  };
-
   m.def(
       "gemm_mxfp8",
-      [mx_dims](f32_array a, f32_array b, int device) {
-        auto [M, N, K] = mx_dims("gemm_mxfp8", a, b);
-        py::array_t<float> c({static_cast<py::ssize_t>(M), static_cast<py::ssize_t>(N)});
-        const float* pa = a.data();
-        const float* pb = b.data();
-        float* pc = c.mutable_data();
-        {
-          py::gil_scoped_release rel;
-          payload::gemm_mxfp8(pa, pb, pc, M, N, K, device);
-        }
-        return c;
+      [](f32_array a, f32_array b, int device) {
+        return gemm_f32("gemm_mxfp8", payload::gemm_mxfp8, a, b, device);
       },
       py::arg("a"), py::arg("b"), py::arg("device") = 0,
       "C (M,N) float32 = mx(a (M,K)) @ mx(b (K,N)): rows of a and columns of b "
@@ -330,27 +427,10 @@ PYBIND11_MODULE(_payload, m) {
 
   m.def(
       "gemm_mxfp8_raw",
-      [mx_dims](u8_array a_codes, u8_array a_scales, u8_array b_codes,
-                u8_array b_scales, int device) {
-        auto [M, N, K] = mx_dims("gemm_mxfp8_raw", a_codes, b_codes);
-        const py::ssize_t blocks = (K + payload::kMxBlock - 1) / payload::kMxBlock;
-        if (a_scales.ndim() != 2 || a_scales.shape(0) != M ||
-            a_scales.shape(1) != blocks)
-          throw py::value_error("gemm_mxfp8_raw: a_scales must be (M, ceil(K/32))");
-        if (b_scales.ndim() != 2 || b_scales.shape(0) != blocks ||
-            b_scales.shape(1) != N)
-          throw py::value_error("gemm_mxfp8_raw: b_scales must be (ceil(K/32), N)");
-        py::array_t<float> c({static_cast<py::ssize_t>(M), static_cast<py::ssize_t>(N)});
-        const uint8_t* pa = a_codes.data();
-        const uint8_t* psa = a_scales.data();
-        const uint8_t* pb = b_codes.data();
-        const uint8_t* psb = b_scales.data();
-        float* pc = c.mutable_data();
-        {
-          py::gil_scoped_release rel;
-          payload::gemm_mxfp8_raw(pa, psa, pb, psb, pc, M, N, K, device);
-        }
-        return c;
+      [](u8_array a_codes, u8_array a_scales, u8_array b_codes, u8_array b_scales,
+         int device) {
+        return gemm_raw("gemm_mxfp8_raw", payload::gemm_mxfp8_raw, any_code, a_codes,
+                        a_scales, b_codes, b_scales, device);
       },
       py::arg("a_codes"), py::arg("a_scales"), py::arg("b_codes"),
       py::arg("b_scales"), py::arg("device") = 0,
@@ -370,19 +450,7 @@ PYBIND11_MODULE(_payload, m) {
   m.def(
       "run_mxgemm",
       [](int mm, int n, int k, int iters, int device) {
-        payload::GemmResult r;
-        {
-          py::gil_scoped_release rel;
-          r = payload::run_mxgemm(mm, n, k, iters, device);
-        }
-        py::dict d;
-        d["m"] = mm;
-        d["n"] = n;
-        d["k"] = k;
-        d["iters"] = iters;
-        d["tflops"] = r.tflops;
-        d["max_err"] = r.max_err;
-        return d;
+        return run_timed_gemm(payload::run_mxgemm, mm, n, k, iters, device);
       },
       py::arg("m") = 4096, py::arg("n") = 4096, py::arg("k") = 2048,
       py::arg("iters") = 10, py::arg("device") = 0,
@@ -391,30 +459,11 @@ PYBIND11_MODULE(_payload, m) {
 
   // ---- MXFP4 ---------------------------------------------------------------
 
-  auto no_nan = [](const char* who, const f32_array& x) {
-    const float* src = x.data();
-    for (py::ssize_t i = 0, n = x.size(); i < n; ++i)
-      if (std::isnan(src[i]))
-        throw py::value_error(std::string(who) + ": x has a NaN element (e2m1 has no NaN)");
-  };
-  auto e2m1_codes = [](const char* who, const u8_array& codes) {
-    const uint8_t* src = codes.data();
-    for (py::ssize_t i = 0, n = codes.size(); i < n; ++i)
-      if (src[i] > 15)
-        throw py::value_error(std::string(who) + ": an e2m1 code must be in 0 .. 15");
-  };
-
   m.def(
       "to_e2m1",
-      [no_nan](f32_array x) {
+      [](f32_array x) {
         no_nan("to_e2m1", x);
-        py::array_t<uint8_t> out(
-            std::vector<py::ssize_t>(x.shape(), x.shape() + x.ndim()));
-        const float* src = x.data();
-        uint8_t* dst = out.mutable_data();
-        for (py::ssize_t i = 0, n = x.size(); i < n; ++i)
-          dst[i] = payload::to_e2m1_sat(src[i]);
-        return out;
+        return map_elements(x, payload::to_e2m1_sat);
       },
       py::arg("x"),
       "float32 -> OCP e2m1 code (uint8, 0..15, bit 3 the sign), nearest value "
@@ -423,15 +472,9 @@ PYBIND11_MODULE(_payload, m) {
 
   m.def(
       "from_e2m1",
-      [e2m1_codes](u8_array codes) {
+      [](u8_array codes) {
         e2m1_codes("from_e2m1", codes);
-        py::array_t<float> out(
-            std::vector<py::ssize_t>(codes.shape(), codes.shape() + codes.ndim()));
-        const uint8_t* src = codes.data();
-        float* dst = out.mutable_data();
-        for (py::ssize_t i = 0, n = codes.size(); i < n; ++i)
-          dst[i] = payload::from_e2m1(src[i]);
-        return out;
+        return map_elements(codes, payload::from_e2m1);
       },
       py::arg("codes"),
       "OCP e2m1 code (uint8, 0..15) -> float32; ValueError on a code above 15; "
@@ -439,24 +482,10 @@ PYBIND11_MODULE(_payload, m) {
 
   m.def(
       "mx4_quantize",
-      [no_nan](f32_array x) {
-        if (x.ndim() < 1)
-          throw py::value_error("mx4_quantize: x must have at least one axis");
-        if (x.shape(x.ndim() - 1) < 1 || x.shape(x.ndim() - 1) > INT32_MAX)
-          throw py::value_error("mx4_quantize: bad length of the last axis");
+      [](f32_array x) {
+        const int K = last_axis("mx4_quantize", "x", x);
         no_nan("mx4_quantize", x);
-        const int K = static_cast<int>(x.shape(x.ndim() - 1));
-        const py::ssize_t blocks = (K + payload::kMxBlock - 1) / payload::kMxBlock;
-        std::vector<py::ssize_t> shape(x.shape(), x.shape() + x.ndim());
-        py::array_t<uint8_t> codes(shape);
-        shape.back() = blocks;
-        py::array_t<uint8_t> scales(shape);
-        const float* src = x.data();
-        uint8_t* pc = codes.mutable_data();
-        uint8_t* ps = scales.mutable_data();
-        for (py::ssize_t r = 0, rows = x.size() / K; r < rows; ++r)
-          payload::mx4_quantize_row(src + r * K, K, pc + r * K, ps + r * blocks);
-        return py::make_tuple(codes, scales);
+        return quantize_rows(x, K, payload::mx4_quantize_row);
       },
       py::arg("x"),
       "OCP MX quantization to e2m1 along the last axis: (codes uint8 [..., K], one "
@@ -465,23 +494,10 @@ PYBIND11_MODULE(_payload, m) {
 
   m.def(
       "pack_fp4",
-      [e2m1_codes](u8_array codes) {
-        if (codes.ndim() < 1)
-          throw py::value_error("pack_fp4: codes must have at least one axis");
-        if (codes.shape(codes.ndim() - 1) < 1 ||
-            codes.shape(codes.ndim() - 1) > INT32_MAX)
-          throw py::value_error("pack_fp4: bad length of the last axis");
+      [](u8_array codes) {
+        const int K = last_axis("pack_fp4", "codes", codes);
         e2m1_codes("pack_fp4", codes);
-        const int K = static_cast<int>(codes.shape(codes.ndim() - 1));
-        const py::ssize_t bytes = (K + 1) / 2;
-        std::vector<py::ssize_t> shape(codes.shape(), codes.shape() + codes.ndim());
-        shape.back() = bytes;
-        py::array_t<uint8_t> out(shape);
-        const uint8_t* src = codes.data();
-        uint8_t* dst = out.mutable_data();
-        for (py::ssize_t r = 0, rows = codes.size() / K; r < rows; ++r)
-          payload::pack_fp4(src + r * K, K, dst + r * bytes);
-        return out;
+        return std::get<0>(map_rows(codes, K, payload::pack_fp4, py::ssize_t{(K + 1) / 2}));
       },
       py::arg("codes"),
       "the device byte image of e2m1 codes along the last axis: uint8 [..., "
@@ -490,17 +506,8 @@ PYBIND11_MODULE(_payload, m) {
 
   m.def(
       "gemm_mxfp4",
-      [mx_dims](f32_array a, f32_array b, int device) {
-        auto [M, N, K] = mx_dims("gemm_mxfp4", a, b);
-        py::array_t<float> c({static_cast<py::ssize_t>(M), static_cast<py::ssize_t>(N)});
-        const float* pa = a.data();
-        const float* pb = b.data();
-        float* pc = c.mutable_data();
-        {
-          py::gil_scoped_release rel;
-          payload::gemm_mxfp4(pa, pb, pc, M, N, K, device);
-        }
-        return c;
+      [](f32_array a, f32_array b, int device) {
+        return gemm_f32("gemm_mxfp4", payload::gemm_mxfp4, a, b, device);
       },
       py::arg("a"), py::arg("b"), py::arg("device") = 0,
       "C (M,N) float32 = mx4(a (M,K)) @ mx4(b (K,N)): rows of a and columns of b "
@@ -509,29 +516,10 @@ PYBIND11_MODULE(_payload, m) {
 
   m.def(
       "gemm_mxfp4_raw",
-      [mx_dims, e2m1_codes](u8_array a_codes, u8_array a_scales, u8_array b_codes,
-                            u8_array b_scales, int device) {
-        auto [M, N, K] = mx_dims("gemm_mxfp4_raw", a_codes, b_codes);
-        const py::ssize_t blocks = (K + payload::kMxBlock - 1) / payload::kMxBlock;
-        if (a_scales.ndim() != 2 || a_scales.shape(0) != M ||
-            a_scales.shape(1) != blocks)
-          throw py::value_error("gemm_mxfp4_raw: a_scales must be (M, ceil(K/32))");
-        if (b_scales.ndim() != 2 || b_scales.shape(0) != blocks ||
-            b_scales.shape(1) != N)
-          throw py::value_error("gemm_mxfp4_raw: b_scales must be (ceil(K/32), N)");
-        e2m1_codes("gemm_mxfp4_raw", a_codes);
-        e2m1_codes("gemm_mxfp4_raw", b_codes);
-        py::array_t<float> c({static_cast<py::ssize_t>(M), static_cast<py::ssize_t>(N)});
-        const uint8_t* pa = a_codes.data();
-        const uint8_t* psa = a_scales.data();
-        const uint8_t* pb = b_codes.data();
-        const uint8_t* psb = b_scales.data();
-        float* pc = c.mutable_data();
-        {
-          py::gil_scoped_release rel;
-          payload::gemm_mxfp4_raw(pa, psa, pb, psb, pc, M, N, K, device);
-        }
-        return c;
+      [](u8_array a_codes, u8_array a_scales, u8_array b_codes, u8_array b_scales,
+         int device) {
+        return gemm_raw("gemm_mxfp4_raw", payload::gemm_mxfp4_raw, e2m1_codes, a_codes,
+                        a_scales, b_codes, b_scales, device);
       },
       py::arg("a_codes"), py::arg("a_scales"), py::arg("b_codes"),
       py::arg("b_scales"), py::arg("device") = 0,
@@ -552,19 +540,7 @@ PYBIND11_MODULE(_payload, m) {
   m.def(
       "run_mx4gemm",
       [](int mm, int n, int k, int iters, int device) {
-        payload::GemmResult r;
-        {
-          py::gil_scoped_release rel;
-          r = payload::run_mx4gemm(mm, n, k, iters, device);
-        }
-        py::dict d;
-        d["m"] = mm;
-        d["n"] = n;
-        d["k"] = k;
-        d["iters"] = iters;
-        d["tflops"] = r.tflops;
-        d["max_err"] = r.max_err;
-        return d;
+        return run_timed_gemm(payload::run_mx4gemm, mm, n, k, iters, device);
       },
       py::arg("m") = 4096, py::arg("n") = 4096, py::arg("k") = 2048,
       py::arg("iters") = 10, py::arg("device") = 0,
@@ -681,34 +657,16 @@ PYBIND11_MODULE(_payload, m) {
                                  py::object lengths, py::object scale, int splits,
                                  int device) {
         const char* who = "attn_decode";
-        if (q.ndim() != 3) throw py::value_error("attn_decode: q must be (B,Hq,128)");
-        if (k.ndim() != 4 || v.ndim() != 4)
-          throw py::value_error("attn_decode: k and v must be (B,Hkv,L,128)");
-        if (q.shape(2) != payload::kAttnD || k.shape(3) != payload::kAttnD)
-          throw py::value_error("attn_decode: head dim must be 128");
-        for (int i = 0; i < 4; ++i)
-          if (k.shape(i) != v.shape(i))
-            throw py::value_error("attn_decode: k and v differ in shape");
-        if (k.shape(0) != q.shape(0))
-          throw py::value_error("attn_decode: q and k differ in batch");
+        attn_operands(who, q, 3, "(B,Hq,128)", k, v);
         const py::ssize_t B = q.shape(0), Hq = q.shape(1), Hkv = k.shape(1),
                           L = k.shape(2);
         attn_shape(who, B, Hq, Hkv, L, splits);
         std::vector<int> lens = attn_lengths(who, lengths, B, L);
-        float sc = 1.0f / std::sqrt(static_cast<float>(payload::kAttnD));
-        if (!scale.is_none()) {
-          sc = scale.cast<float>();
-          if (!std::isfinite(sc)) throw py::value_error("attn_decode: scale not finite");
-        }
+        const float sc = attn_scale(who, scale);
+        attn_finite(who, q, k, v);
         const float* pq = q.data();
         const float* pk = k.data();
         const float* pv = v.data();
-        for (py::ssize_t i = 0, n = q.size(); i < n; ++i)
-          if (!std::isfinite(pq[i]))
-            throw py::value_error("attn_decode: q has a non-finite element");
-        for (py::ssize_t i = 0, n = k.size(); i < n; ++i)
-          if (!std::isfinite(pk[i]) || !std::isfinite(pv[i]))
-            throw py::value_error("attn_decode: k or v has a non-finite element");
         py::array_t<float> o({B, Hq, static_cast<py::ssize_t>(payload::kAttnD)});
         float* po = o.mutable_data();
         {
@@ -828,35 +786,17 @@ PYBIND11_MODULE(_payload, m) {
       [prefill_shape](f32_array q, f32_array k, f32_array v, bool causal,
                       py::object scale, int device) {
         const char* who = "attn_prefill";
-        if (q.ndim() != 4) throw py::value_error("attn_prefill: q must be (B,Hq,L,128)");
-        if (k.ndim() != 4 || v.ndim() != 4)
-          throw py::value_error("attn_prefill: k and v must be (B,Hkv,L,128)");
-        if (q.shape(3) != payload::kAttnD || k.shape(3) != payload::kAttnD)
-          throw py::value_error("attn_prefill: head dim must be 128");
-        for (int i = 0; i < 4; ++i)
-          if (k.shape(i) != v.shape(i))
-            throw py::value_error("attn_prefill: k and v differ in shape");
-        if (k.shape(0) != q.shape(0))
-          throw py::value_error("attn_prefill: q and k differ in batch");
+        attn_operands(who, q, 4, "(B,Hq,L,128)", k, v);
         if (k.shape(2) != q.shape(2))
           throw py::value_error("attn_prefill: q and k differ in length");
         const py::ssize_t B = q.shape(0), Hq = q.shape(1), Hkv = k.shape(1),
                           L = q.shape(2);
         prefill_shape(who, B, Hq, Hkv, L);
-        float sc = 1.0f / std::sqrt(static_cast<float>(payload::kAttnD));
-        if (!scale.is_none()) {
-          sc = scale.cast<float>();
-          if (!std::isfinite(sc)) throw py::value_error("attn_prefill: scale not finite");
-        }
+        const float sc = attn_scale(who, scale);
+        attn_finite(who, q, k, v);
         const float* pq = q.data();
         const float* pk = k.data();
         const float* pv = v.data();
-        for (py::ssize_t i = 0, n = q.size(); i < n; ++i)
-          if (!std::isfinite(pq[i]))
-            throw py::value_error("attn_prefill: q has a non-finite element");
-        for (py::ssize_t i = 0, n = k.size(); i < n; ++i)
-          if (!std::isfinite(pk[i]) || !std::isfinite(pv[i]))
-            throw py::value_error("attn_prefill: k or v has a non-finite element");
         py::array_t<float> o({B, Hq, L, static_cast<py::ssize_t>(payload::kAttnD)});
         float* po = o.mutable_data();
         {

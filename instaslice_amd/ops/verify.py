@@ -99,8 +99,27 @@ def judge(report: dict, profile_name: str) -> dict:
         failed.append("xcds")
     if not _is_zero(report.get("membw_bad_units")):
         failed.append("membw")
+    return _verdict(report, profile_name, failed)
+
+
+def _verdict(report: dict, profile_name: str, failed: list) -> dict:
     return {"ok": not failed, "failed": failed, "profile": profile_name,
             "report": report}
+
+
+def _judge_one(report: dict, profile_name: str, name: str,
+               clean: Callable[[dict], bool]) -> dict:
+    # a probe with one judged item: `name` fails unless `clean(report)`
+    parse_profile_name(profile_name)
+    return _verdict(report, profile_name, [] if clean(report) else [name])
+
+
+def _is_count(value) -> bool:
+    return isinstance(value, int) and not isinstance(value, bool)
+
+
+def _counts_from_one(report: dict, keys) -> bool:
+    return all(_is_count(report.get(key)) and report[key] >= 1 for key in keys)
 
 
 def _not_run(profile_name: str, reason: str, report: Optional[dict] = None) -> dict:
@@ -108,24 +127,26 @@ def _not_run(profile_name: str, reason: str, report: Optional[dict] = None) -> d
             "reason": reason, "report": report}
 
 
-def run(profile_name: str, env: Optional[Dict[str, str]] = None,
-        runner: Callable = subprocess.run) -> dict:
-    """Run `instaslice-payload verify` in a fresh child with `env` (the pod's
-    ROCR_VISIBLE_DEVICES and the like, laid over this process's environment)
-    and judge its report. Every way the child can fail to produce a report
-    comes back as `ok: False` with a `reason`; only an unparseable profile
-    name raises (ValueError)."""
-    want = expected_xcds(profile_name)
+def _run_child(profile_name: str, argv_tail: list, timeout_s: float, marker: str,
+               judge_report: Callable, env: Optional[Dict[str, str]],
+               runner: Callable) -> dict:
+    """Run `instaslice-payload` with `argv_tail` (the verb first) in a fresh
+    child with `env` laid over this process's environment, and judge the last
+    JSON line of its output with `judge_report(report)`. `marker` is the field
+    that tells a real report from the binary's catch-all error line. Every way
+    the child can fail to produce a report comes back as `ok: False` with a
+    `reason`."""
+    verb = argv_tail[0]
     child_env = dict(os.environ)
     child_env.update({k: str(v) for k, v in (env or {}).items()})
     try:
-        proc = runner([BIN_PATH, "verify", str(want)], capture_output=True,
-                      text=True, timeout=CHILD_TIMEOUT_S, env=child_env)
+        proc = runner([BIN_PATH, *argv_tail], capture_output=True, text=True,
+                      timeout=timeout_s, env=child_env)
     except FileNotFoundError:
         return _not_run(profile_name, f"payload binary not found: {BIN_PATH}")
     except subprocess.TimeoutExpired:
         return _not_run(profile_name,
-                        f"verify timed out after {CHILD_TIMEOUT_S:.0f} s")
+                        f"{verb} timed out after {timeout_s:.0f} s")
     except OSError as e:
         return _not_run(profile_name, f"could not start payload binary: {e}")
 
@@ -138,19 +159,30 @@ def run(profile_name: str, env: Optional[Dict[str, str]] = None,
         tail = (proc.stdout or "").strip()[-200:]
         return _not_run(profile_name,
                         f"non-JSON output (exit {proc.returncode}): {tail!r}")
-    if "xcds_visible" not in report:
+    if marker not in report:
         # the binary's catch-all error line: {"ok": false, "error": "..."}
         return _not_run(profile_name,
-                        f"verify failed (exit {proc.returncode}): "
+                        f"{verb} failed (exit {proc.returncode}): "
                         f"{report.get('error', 'no report fields')}", report)
-    verdict = judge(report, profile_name)
-    if proc.returncode != 0 and verdict["ok"]:
-        # the fields look clean but the child says otherwise: believe the exit
+    verdict = judge_report(report)
+    if proc.returncode != 0:
+        # clean-looking fields do not outvote a non-zero exit
         verdict["ok"] = False
         verdict["reason"] = f"payload exited {proc.returncode}"
-    elif proc.returncode != 0:
-        verdict["reason"] = f"payload exited {proc.returncode}"
     return verdict
+
+
+def run(profile_name: str, env: Optional[Dict[str, str]] = None,
+        runner: Callable = subprocess.run) -> dict:
+    """Run `instaslice-payload verify` in a fresh child with `env` (the pod's
+    ROCR_VISIBLE_DEVICES and the like, laid over this process's environment)
+    and judge its report. Every way the child can fail to produce a report
+    comes back as `ok: False` with a `reason`; only an unparseable profile
+    name raises (ValueError)."""
+    want = expected_xcds(profile_name)
+    return _run_child(profile_name, ["verify", str(want)], CHILD_TIMEOUT_S,
+                      "xcds_visible", lambda report: judge(report, profile_name),
+                      env, runner)
 
 
 # ---- memcheck ---------------------------------------------------------------
@@ -166,26 +198,19 @@ GIB = 1 << 30  # a profile's "GB" is 2^30 bytes, as in the report's total_mem_gb
 MEMCHECK_TIMEOUT_S = 120.0
 
 
-def _is_count(value) -> bool:
-    return isinstance(value, int) and not isinstance(value, bool)
-
-
 def judge_memcheck(report: dict, profile_name: str, want_bytes: int) -> dict:
     """Judge an `instaslice-payload memcheck` report: "memory" fails unless
     the whole of `want_bytes` (rounded down to 16) was swept at least once and
     no word came back wrong. Pure; the report's own `ok` is not trusted.
     ValueError on a profile name that does not parse."""
-    parse_profile_name(profile_name)
-    clean = (_is_zero(report.get("bad_words"))
-             and _is_count(report.get("first_bad_offset"))
-             and report["first_bad_offset"] == -1
-             and _is_count(report.get("bytes"))
-             and report["bytes"] == int(want_bytes) // 16 * 16
-             and _is_count(report.get("passes"))
-             and report["passes"] >= 1)
-    failed = [] if clean else ["memory"]
-    return {"ok": not failed, "failed": failed, "profile": profile_name,
-            "report": report}
+    def clean(report):
+        return (_is_zero(report.get("bad_words"))
+                and _is_count(report.get("first_bad_offset"))
+                and report["first_bad_offset"] == -1
+                and _is_count(report.get("bytes"))
+                and report["bytes"] == int(want_bytes) // 16 * 16
+                and _counts_from_one(report, ("passes",)))
+    return _judge_one(report, profile_name, "memory", clean)
 
 
 def memcheck_bytes(profile_name: str, gb: Optional[float] = None,
@@ -221,56 +246,26 @@ def run_memcheck(profile_name: str, env: Optional[Dict[str, str]] = None,
     want_bytes = memcheck_bytes(profile_name, gb=gb, fraction=fraction)
     if not _is_count(passes) or passes < 1:
         raise ValueError(f"passes must be an integer >= 1, got {passes!r}")
-    child_env = dict(os.environ)
-    child_env.update({k: str(v) for k, v in (env or {}).items()})
-    try:
-        proc = runner([BIN_PATH, "memcheck", str(want_bytes), str(passes)],
-                      capture_output=True, text=True,
-                      timeout=MEMCHECK_TIMEOUT_S, env=child_env)
-    except FileNotFoundError:
-        return _not_run(profile_name, f"payload binary not found: {BIN_PATH}")
-    except subprocess.TimeoutExpired:
-        return _not_run(profile_name,
-                        f"memcheck timed out after {MEMCHECK_TIMEOUT_S:.0f} s")
-    except OSError as e:
-        return _not_run(profile_name, f"could not start payload binary: {e}")
-
-    lines = [ln for ln in (proc.stdout or "").splitlines() if ln.strip()]
-    try:
-        report = json.loads(lines[-1]) if lines else None
-    except ValueError:
-        report = None
-    if not isinstance(report, dict):
-        tail = (proc.stdout or "").strip()[-200:]
-        return _not_run(profile_name,
-                        f"non-JSON output (exit {proc.returncode}): {tail!r}")
-    if "bad_words" not in report:
-        # the binary's catch-all error line: {"ok": false, "error": "..."}
-        return _not_run(profile_name,
-                        f"memcheck failed (exit {proc.returncode}): "
-                        f"{report.get('error', 'no report fields')}", report)
-    verdict = judge_memcheck(report, profile_name, want_bytes)
-    if proc.returncode != 0:
-        # clean-looking fields do not outvote a non-zero exit
-        verdict["ok"] = False
-        verdict["reason"] = f"payload exited {proc.returncode}"
-    return verdict
+    return _run_child(profile_name, ["memcheck", str(want_bytes), str(passes)],
+                      MEMCHECK_TIMEOUT_S, "bad_words",
+                      lambda report: judge_memcheck(report, profile_name,
+                                                    want_bytes),
+                      env, runner)
 
 
 # ---- mxgemm -----------------------------------------------------------------
+
+def _mx_fields_clean(report: dict) -> bool:
+    return _is_zero(report.get("max_err")) \
+        and _counts_from_one(report, ("m", "n", "k", "iters"))
+
 
 def judge_mxgemm(report: dict, profile_name: str) -> dict:
     """Judge an `instaslice-payload mxgemm` report: "mxgemm" fails unless
     `max_err` is a numeric zero and `m`, `n`, `k`, `iters` are integer counts
     >= 1. `tflops` is carried and never judged. Pure; the report's own `ok`
     is not trusted. ValueError on a profile name that does not parse."""
-    parse_profile_name(profile_name)
-    clean = (_is_zero(report.get("max_err"))
-             and all(_is_count(report.get(key)) and report[key] >= 1
-                     for key in ("m", "n", "k", "iters")))
-    failed = [] if clean else ["mxgemm"]
-    return {"ok": not failed, "failed": failed, "profile": profile_name,
-            "report": report}
+    return _judge_one(report, profile_name, "mxgemm", _mx_fields_clean)
 
 
 def run_mxgemm(profile_name: str, env: Optional[Dict[str, str]] = None,
@@ -281,39 +276,9 @@ def run_mxgemm(profile_name: str, env: Optional[Dict[str, str]] = None,
     with a `reason`, and only an unparseable profile name raises
     (ValueError)."""
     parse_profile_name(profile_name)
-    child_env = dict(os.environ)
-    child_env.update({k: str(v) for k, v in (env or {}).items()})
-    try:
-        proc = runner([BIN_PATH, "mxgemm"], capture_output=True, text=True,
-                      timeout=CHILD_TIMEOUT_S, env=child_env)
-    except FileNotFoundError:
-        return _not_run(profile_name, f"payload binary not found: {BIN_PATH}")
-    except subprocess.TimeoutExpired:
-        return _not_run(profile_name,
-                        f"mxgemm timed out after {CHILD_TIMEOUT_S:.0f} s")
-    except OSError as e:
-        return _not_run(profile_name, f"could not start payload binary: {e}")
-
-    lines = [ln for ln in (proc.stdout or "").splitlines() if ln.strip()]
-    try:
-        report = json.loads(lines[-1]) if lines else None
-    except ValueError:
-        report = None
-    if not isinstance(report, dict):
-        tail = (proc.stdout or "").strip()[-200:]
-        return _not_run(profile_name,
-                        f"non-JSON output (exit {proc.returncode}): {tail!r}")
-    if "max_err" not in report:
-        # the binary's catch-all error line: {"ok": false, "error": "..."}
-        return _not_run(profile_name,
-                        f"mxgemm failed (exit {proc.returncode}): "
-                        f"{report.get('error', 'no report fields')}", report)
-    verdict = judge_mxgemm(report, profile_name)
-    if proc.returncode != 0:
-        # clean-looking fields do not outvote a non-zero exit
-        verdict["ok"] = False
-        verdict["reason"] = f"payload exited {proc.returncode}"
-    return verdict
+    return _run_child(profile_name, ["mxgemm"], CHILD_TIMEOUT_S, "max_err",
+                      lambda report: judge_mxgemm(report, profile_name),
+                      env, runner)
 
 
 # ---- mx4gemm ----------------------------------------------------------------
@@ -323,13 +288,7 @@ def judge_mx4gemm(report: dict, profile_name: str) -> dict:
     `max_err` is a numeric zero and `m`, `n`, `k`, `iters` are integer counts
     >= 1. `tflops` is carried and never judged. Pure; the report's own `ok`
     is not trusted. ValueError on a profile name that does not parse."""
-    parse_profile_name(profile_name)
-    clean = (_is_zero(report.get("max_err"))
-             and all(_is_count(report.get(key)) and report[key] >= 1
-                     for key in ("m", "n", "k", "iters")))
-    failed = [] if clean else ["mx4gemm"]
-    return {"ok": not failed, "failed": failed, "profile": profile_name,
-            "report": report}
+    return _judge_one(report, profile_name, "mx4gemm", _mx_fields_clean)
 
 
 def run_mx4gemm(profile_name: str, env: Optional[Dict[str, str]] = None,
@@ -340,39 +299,9 @@ def run_mx4gemm(profile_name: str, env: Optional[Dict[str, str]] = None,
     with a `reason`, and only an unparseable profile name raises
     (ValueError)."""
     parse_profile_name(profile_name)
-    child_env = dict(os.environ)
-    child_env.update({k: str(v) for k, v in (env or {}).items()})
-    try:
-        proc = runner([BIN_PATH, "mx4gemm"], capture_output=True, text=True,
-                      timeout=CHILD_TIMEOUT_S, env=child_env)
-    except FileNotFoundError:
-        return _not_run(profile_name, f"payload binary not found: {BIN_PATH}")
-    except subprocess.TimeoutExpired:
-        return _not_run(profile_name,
-                        f"mx4gemm timed out after {CHILD_TIMEOUT_S:.0f} s")
-    except OSError as e:
-        return _not_run(profile_name, f"could not start payload binary: {e}")
-
-    lines = [ln for ln in (proc.stdout or "").splitlines() if ln.strip()]
-    try:
-        report = json.loads(lines[-1]) if lines else None
-    except ValueError:
-        report = None
-    if not isinstance(report, dict):
-        tail = (proc.stdout or "").strip()[-200:]
-        return _not_run(profile_name,
-                        f"non-JSON output (exit {proc.returncode}): {tail!r}")
-    if "max_err" not in report:
-        # the binary's catch-all error line: {"ok": false, "error": "..."}
-        return _not_run(profile_name,
-                        f"mx4gemm failed (exit {proc.returncode}): "
-                        f"{report.get('error', 'no report fields')}", report)
-    verdict = judge_mx4gemm(report, profile_name)
-    if proc.returncode != 0:
-        # clean-looking fields do not outvote a non-zero exit
-        verdict["ok"] = False
-        verdict["reason"] = f"payload exited {proc.returncode}"
-    return verdict
+    return _run_child(profile_name, ["mx4gemm"], CHILD_TIMEOUT_S, "max_err",
+                      lambda report: judge_mx4gemm(report, profile_name),
+                      env, runner)
 
 
 # ---- attn -------------------------------------------------------------------
@@ -389,6 +318,13 @@ def _is_real(value) -> bool:
         and math.isfinite(value)
 
 
+def _attn_fields_clean(report: dict, max_rel: float) -> bool:
+    return (_is_zero(report.get("max_err"))
+            and _is_real(report.get("max_rel"))
+            and 0 <= report["max_rel"] <= max_rel
+            and _counts_from_one(report, ("batch", "hq", "hkv", "len", "iters")))
+
+
 def judge_attn(report: dict, profile_name: str) -> dict:
     """Judge an `instaslice-payload attn` report: "attn" fails unless
     `max_err` is a numeric zero, `max_rel` is a real number in [0, 2**-8] and
@@ -396,15 +332,8 @@ def judge_attn(report: dict, profile_name: str) -> dict:
     `kv_gb_per_s`, `steps_per_s` and `tok_per_s` are carried and never judged.
     Pure; the report's own `ok` is not trusted. ValueError on a profile name
     that does not parse."""
-    parse_profile_name(profile_name)
-    clean = (_is_zero(report.get("max_err"))
-             and _is_real(report.get("max_rel"))
-             and 0 <= report["max_rel"] <= ATTN_MAX_REL
-             and all(_is_count(report.get(key)) and report[key] >= 1
-                     for key in ("batch", "hq", "hkv", "len", "iters")))
-    failed = [] if clean else ["attn"]
-    return {"ok": not failed, "failed": failed, "profile": profile_name,
-            "report": report}
+    return _judge_one(report, profile_name, "attn",
+                      lambda r: _attn_fields_clean(r, ATTN_MAX_REL))
 
 
 def run_attn(profile_name: str, env: Optional[Dict[str, str]] = None,
@@ -414,39 +343,9 @@ def run_attn(profile_name: str, env: Optional[Dict[str, str]] = None,
     `run_mxgemm`: every way the child can fail comes back as `ok: False` with
     a `reason`, and only an unparseable profile name raises (ValueError)."""
     parse_profile_name(profile_name)
-    child_env = dict(os.environ)
-    child_env.update({k: str(v) for k, v in (env or {}).items()})
-    try:
-        proc = runner([BIN_PATH, "attn"], capture_output=True, text=True,
-                      timeout=CHILD_TIMEOUT_S, env=child_env)
-    except FileNotFoundError:
-        return _not_run(profile_name, f"payload binary not found: {BIN_PATH}")
-    except subprocess.TimeoutExpired:
-        return _not_run(profile_name,
-                        f"attn timed out after {CHILD_TIMEOUT_S:.0f} s")
-    except OSError as e:
-        return _not_run(profile_name, f"could not start payload binary: {e}")
-
-    lines = [ln for ln in (proc.stdout or "").splitlines() if ln.strip()]
-    try:
-        report = json.loads(lines[-1]) if lines else None
-    except ValueError:
-        report = None
-    if not isinstance(report, dict):
-        tail = (proc.stdout or "").strip()[-200:]
-        return _not_run(profile_name,
-                        f"non-JSON output (exit {proc.returncode}): {tail!r}")
-    if "max_err" not in report:
-        # the binary's catch-all error line: {"ok": false, "error": "..."}
-        return _not_run(profile_name,
-                        f"attn failed (exit {proc.returncode}): "
-                        f"{report.get('error', 'no report fields')}", report)
-    verdict = judge_attn(report, profile_name)
-    if proc.returncode != 0:
-        # clean-looking fields do not outvote a non-zero exit
-        verdict["ok"] = False
-        verdict["reason"] = f"payload exited {proc.returncode}"
-    return verdict
+    return _run_child(profile_name, ["attn"], CHILD_TIMEOUT_S, "max_err",
+                      lambda report: judge_attn(report, profile_name),
+                      env, runner)
 
 
 # ---- prefill ----------------------------------------------------------------
@@ -464,16 +363,9 @@ def judge_prefill(report: dict, profile_name: str) -> dict:
     is a bool. `tflops` and `tok_per_s` are carried and never judged. Pure; the
     report's own `ok` is not trusted. ValueError on a profile name that does
     not parse."""
-    parse_profile_name(profile_name)
-    clean = (_is_zero(report.get("max_err"))
-             and _is_real(report.get("max_rel"))
-             and 0 <= report["max_rel"] <= PREFILL_MAX_REL
-             and all(_is_count(report.get(key)) and report[key] >= 1
-                     for key in ("batch", "hq", "hkv", "len", "iters"))
-             and isinstance(report.get("causal"), bool))
-    failed = [] if clean else ["prefill"]
-    return {"ok": not failed, "failed": failed, "profile": profile_name,
-            "report": report}
+    return _judge_one(report, profile_name, "prefill",
+                      lambda r: _attn_fields_clean(r, PREFILL_MAX_REL)
+                      and isinstance(r.get("causal"), bool))
 
 
 def run_prefill(profile_name: str, env: Optional[Dict[str, str]] = None,
@@ -483,36 +375,6 @@ def run_prefill(profile_name: str, env: Optional[Dict[str, str]] = None,
     as `run_attn`: every way the child can fail comes back as `ok: False` with
     a `reason`, and only an unparseable profile name raises (ValueError)."""
     parse_profile_name(profile_name)
-    child_env = dict(os.environ)
-    child_env.update({k: str(v) for k, v in (env or {}).items()})
-    try:
-        proc = runner([BIN_PATH, "prefill"], capture_output=True, text=True,
-                      timeout=CHILD_TIMEOUT_S, env=child_env)
-    except FileNotFoundError:
-        return _not_run(profile_name, f"payload binary not found: {BIN_PATH}")
-    except subprocess.TimeoutExpired:
-        return _not_run(profile_name,
-                        f"prefill timed out after {CHILD_TIMEOUT_S:.0f} s")
-    except OSError as e:
-        return _not_run(profile_name, f"could not start payload binary: {e}")
-
-    lines = [ln for ln in (proc.stdout or "").splitlines() if ln.strip()]
-    try:
-        report = json.loads(lines[-1]) if lines else None
-    except ValueError:
-        report = None
-    if not isinstance(report, dict):
-        tail = (proc.stdout or "").strip()[-200:]
-        return _not_run(profile_name,
-                        f"non-JSON output (exit {proc.returncode}): {tail!r}")
-    if "max_err" not in report:
-        # the binary's catch-all error line: {"ok": false, "error": "..."}
-        return _not_run(profile_name,
-                        f"prefill failed (exit {proc.returncode}): "
-                        f"{report.get('error', 'no report fields')}", report)
-    verdict = judge_prefill(report, profile_name)
-    if proc.returncode != 0:
-        # clean-looking fields do not outvote a non-zero exit
-        verdict["ok"] = False
-        verdict["reason"] = f"payload exited {proc.returncode}"
-    return verdict
+    return _run_child(profile_name, ["prefill"], CHILD_TIMEOUT_S, "max_err",
+                      lambda report: judge_prefill(report, profile_name),
+                      env, runner)
