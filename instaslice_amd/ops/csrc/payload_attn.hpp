@@ -58,8 +58,9 @@
 // and forms no address outside its buffers for any shape.
 //
 // Included by payload_core.hpp after the others (needs HIP_CHECK, kBlock,
-// bf16x8, f32x4, to_bf16_rne, detail::DeviceBuffer, detail::Event,
-// detail::round_up and detail::note_err).
+// bf16x8, f32x4, to_bf16_rne, detail::DeviceBuffer, detail::time_launches,
+// detail::round_up and detail::note_err). The host layer starts with what the
+// prefill payload (payload_prefill.hpp) shares with this one.
 
 #pragma once
 
@@ -74,7 +75,7 @@ constexpr int kAttnChunk = 32;           // keys per wave iteration
 constexpr int kAttnWaves = kBlock / 64;  // partials per split
 constexpr int kAttnMaxGroup = 16;        // query heads per kv head
 constexpr int kAttnMaxSplits = 64;
-constexpr double kAttnRelBound = 1.0 / 256;  // run_attn_check's dense bound
+constexpr double kAttnRelBound = 1.0 / 256;  // dense bound of both attention checks
 constexpr int kAttnChunkElems = kAttnChunk * kAttnD;  // per tensor and chunk
 
 static_assert(kAttnD % 32 == 0 && kAttnD % 16 == 0, "whole MFMA steps only");
@@ -348,9 +349,10 @@ __global__ __launch_bounds__(kBlock) void attn_fill_kv_kernel(
 
 // ---- host layer ----------------------------------------------------------
 
+// what run_attn_check and run_prefill_check return
 struct AttnCheck {
   double max_err = 0;  // selection pattern: expect exactly 0
-  double max_rel = 0;  // dense pattern: max |o - ref| / max |v|, <= 2^-8
+  double max_rel = 0;  // dense pattern: max |o - ref| / max |v|, <= kAttnRelBound
 };
 
 struct AttnResult {
@@ -362,29 +364,85 @@ struct AttnResult {
 
 namespace detail {
 
+// What both attention payloads ask of a shape; returns G = Hq / Hkv. `who`
+// heads the messages. The arguments are 64-bit here and in the two checks
+// built on it, so that a caller can check array extents before it narrows
+// them to int.
+inline long long attn_group(const char* who, long long b, long long hq, long long hkv,
+                            long long len) {
+  if (b < 1 || hq < 1 || hkv < 1 || len < 1)
+    throw std::invalid_argument(std::string(who) + ": B, Hq, Hkv and L must be >= 1");
+  if (hq % hkv != 0)
+    throw std::invalid_argument(std::string(who) + ": Hq must be a multiple of Hkv");
+  return hq / hkv;
+}
+
+// What both problems are: a checked shape, with the group size its check
+// returned, on a device.
+struct AttnShape {
+  int B, Hq, Hkv, L, G, device;
+};
+
+inline float attn_default_scale() { return 1.0f / std::sqrt(static_cast<float>(kAttnD)); }
+
+// the kernels' softmax is in base 2: scale * log2(e)
+inline float attn_c2(float scale) { return scale * 1.4426950408889634f; }
+
+// row t of the 16 spread rows that a timed run checks, out of `rows`
+inline size_t attn_spread_row(int t, size_t rows) {
+  return (static_cast<size_t>(t) * 1031 + 17) % rows;
+}
+
+// fp64 reference of one output row over its first n keys (all of them in
+// decode and without a mask, i + 1 of them for row i under the causal mask),
+// from the row's q and the float tensors k and v of its kv head (n x 128 or
+// longer); w is scratch of n doubles
+inline void attn_ref_row(double* out, const float* qr, const float* kh, const float* vh,
+                         int n, double scale, std::vector<double>& w) {
+  double mx = -INFINITY;
+  for (int t = 0; t < n; ++t) {
+    const float* kr = kh + static_cast<size_t>(t) * kAttnD;
+    double s = 0;
+    for (int d = 0; d < kAttnD; ++d) s += static_cast<double>(qr[d]) * kr[d];
+    w[t] = s * scale;
+    mx = std::max(mx, w[t]);
+  }
+  double den = 0;
+  for (int t = 0; t < n; ++t) den += (w[t] = std::exp(w[t] - mx));
+  for (int d = 0; d < kAttnD; ++d) {
+    double num = 0;
+    for (int t = 0; t < n; ++t) num += w[t] * vh[static_cast<size_t>(t) * kAttnD + d];
+    out[d] = num / den;
+  }
+}
+
+}  // namespace detail
+
+// The limits of the decode payload, or std::invalid_argument; no HIP call.
+// Returns Hq / Hkv.
+inline int attn_decode_shape(long long B, long long Hq, long long Hkv, long long L,
+                             long long splits = 0) {
+  const long long G = detail::attn_group("attn", B, Hq, Hkv, L);
+  if (G > kAttnMaxGroup)
+    throw std::invalid_argument("attn: Hq / Hkv must be <= 16");
+  if (splits < 0 || splits > kAttnMaxSplits)
+    throw std::invalid_argument("attn: splits must be in 0 .. 64");
+  if (B > 65535 || Hkv > 65535 || L > (1 << 28))
+    throw std::invalid_argument("attn: shape too large");
+  return static_cast<int>(G);
+}
+
+namespace detail {
+
 // Shape, device buffers and launch of one decode problem.
-struct AttnProblem {
-  int B, Hq, Hkv, L, G, splits;
+struct AttnProblem : AttnShape {
+  int splits;
   size_t Lp;
-  int device;
   DeviceBuffer dq, dk, dvt, dlens, dpm, dpl, dpo, dout;
 
   AttnProblem(int b, int hq, int hkv, int len, int want_splits, int dev)
-      : B(b), Hq(hq), Hkv(hkv), L(len), device(dev) {
-    if (b < 1 || hq < 1 || hkv < 1 || len < 1)
-      throw std::invalid_argument("attn: B, Hq, Hkv and L must be >= 1");
-    if (hq % hkv != 0)
-      throw std::invalid_argument("attn: Hq must be a multiple of Hkv");
-    G = hq / hkv;
-    if (G > kAttnMaxGroup)
-      throw std::invalid_argument("attn: Hq / Hkv must be <= 16");
-    if (want_splits < 0 || want_splits > kAttnMaxSplits)
-      throw std::invalid_argument("attn: splits must be in 0 .. 64");
-    if (b > 65535 || hkv > 65535 || len > (1 << 28))
-      throw std::invalid_argument("attn: shape too large");
-    Lp = round_up(len, kAttnChunk);
-    splits = want_splits;
-  }
+      : AttnShape{b, hq, hkv, len, attn_decode_shape(b, hq, hkv, len, want_splits), dev},
+        splits(want_splits), Lp(round_up(len, kAttnChunk)) {}
 
   static void check_lens(const int* lens, int B, int L) {
     if (!lens) return;
@@ -471,7 +529,7 @@ struct AttnProblem {
   }
 
   void launch(float scale) const {
-    const float c2 = scale * 1.4426950408889634f;
+    const float c2 = attn_c2(scale);
     dim3 grid(static_cast<unsigned>(splits), static_cast<unsigned>(Hkv),
               static_cast<unsigned>(B));
     hipLaunchKernelGGL(attn_decode_kernel, grid, dim3(kBlock), 0, 0,
@@ -491,7 +549,14 @@ struct AttnProblem {
   }
 };
 
-inline float attn_default_scale() { return 1.0f / std::sqrt(static_cast<float>(kAttnD)); }
+// q (B, Hq, 128) of the selection pattern
+inline void attn_pattern_q(float* q, int B, int Hq) {
+  for (int b = 0; b < B; ++b)
+    for (int h = 0; h < Hq; ++h)
+      for (int d = 0; d < kAttnD; ++d)
+        q[(static_cast<size_t>(b) * Hq + h) * kAttnD + d] =
+            static_cast<float>(attn_pat_q(b, h, d));
+}
 
 // expected output row (b, h) of the selection pattern: sum of v over the
 // selected keys, divided by their (power of two) count
@@ -544,17 +609,14 @@ inline void attn_decode(const float* q, const float* k, const float* v,
 inline void attn_check_pattern(float* q, float* k, float* v, float* expected,
                                int B, int Hq, int Hkv, int L,
                                const int* lens = nullptr) {
-  detail::AttnProblem shape(B, Hq, Hkv, L, 0, 0);  // validation only
+  const int G = attn_decode_shape(B, Hq, Hkv, L);
   detail::AttnProblem::check_lens(lens, B, L);
-  const int G = shape.G;
+  detail::attn_pattern_q(q, B, Hq);
   for (int b = 0; b < B; ++b) {
     const int len = lens ? lens[b] : L;
-    for (int h = 0; h < Hq; ++h) {
-      float* qr = q + (static_cast<size_t>(b) * Hq + h) * kAttnD;
-      for (int d = 0; d < kAttnD; ++d) qr[d] = static_cast<float>(attn_pat_q(b, h, d));
+    for (int h = 0; h < Hq; ++h)
       detail::attn_pattern_row(expected + (static_cast<size_t>(b) * Hq + h) * kAttnD,
                                b, h, G, len);
-    }
     for (int g = 0; g < Hkv; ++g)
       for (int t = 0; t < L; ++t) {
         const size_t off = ((static_cast<size_t>(b) * Hkv + g) * L + t) * kAttnD;
@@ -576,8 +638,8 @@ inline void attn_check_pattern(float* q, float* k, float* v, float* expected,
 // doubles that.
 inline AttnCheck run_attn_check(int B, int Hq, int Hkv, int L, int splits = 0,
                                 int device = 0) {
-  detail::AttnProblem shape(B, Hq, Hkv, L, splits, device);  // validate first
-  const size_t nq = shape.rows() * kAttnD;
+  const int G = attn_decode_shape(B, Hq, Hkv, L, splits);  // validate first
+  const size_t nq = static_cast<size_t>(B) * Hq * kAttnD;
   const size_t nkv = static_cast<size_t>(B) * Hkv * L * kAttnD;
   const float scale = detail::attn_default_scale();
   std::vector<float> q(nq), k(nkv), v(nkv), want(nq), got(nq);
@@ -599,31 +661,16 @@ inline AttnCheck run_attn_check(int B, int Hq, int Hkv, int L, int splits = 0,
   }
   attn_decode(q.data(), k.data(), v.data(), nullptr, got.data(), B, Hq, Hkv, L,
               scale, splits, device);
-  const int G = shape.G;
-  std::vector<double> w(L);
+  std::vector<double> w(L), ref(kAttnD);
   double max_abs = 0;
   for (int b = 0; b < B; ++b)
     for (int h = 0; h < Hq; ++h) {
       const size_t bg = static_cast<size_t>(b) * Hkv + h / G;
-      const float* qr = q.data() + (static_cast<size_t>(b) * Hq + h) * kAttnD;
-      double mx = -INFINITY;
-      for (int t = 0; t < L; ++t) {
-        const float* kr = k.data() + (bg * L + t) * kAttnD;
-        double s = 0;
-        for (int d = 0; d < kAttnD; ++d) s += static_cast<double>(qr[d]) * kr[d];
-        w[t] = s * static_cast<double>(scale);
-        mx = std::max(mx, w[t]);
-      }
-      double den = 0;
-      for (int t = 0; t < L; ++t) den += (w[t] = std::exp(w[t] - mx));
-      for (int d = 0; d < kAttnD; ++d) {
-        double num = 0;
-        for (int t = 0; t < L; ++t)
-          num += w[t] * v[(bg * L + t) * kAttnD + d];
-        detail::note_err(max_abs, std::fabs(
-            static_cast<double>(got[(static_cast<size_t>(b) * Hq + h) * kAttnD + d]) -
-            num / den));
-      }
+      const size_t at = (static_cast<size_t>(b) * Hq + h) * kAttnD;
+      detail::attn_ref_row(ref.data(), q.data() + at, k.data() + bg * L * kAttnD,
+                           v.data() + bg * L * kAttnD, L, static_cast<double>(scale), w);
+      for (int d = 0; d < kAttnD; ++d)
+        detail::note_err(max_abs, std::fabs(static_cast<double>(got[at + d]) - ref[d]));
     }
   r.max_rel = vmax > 0 ? max_abs / vmax : max_abs;
   return r;
@@ -641,11 +688,7 @@ inline AttnResult run_attn(int B = 32, int Hq = 64, int Hkv = 8, int L = 4096,
   detail::AttnProblem p(B, Hq, Hkv, L, splits, device);
   p.alloc();
   std::vector<float> q(p.rows() * kAttnD);
-  for (int b = 0; b < B; ++b)
-    for (int h = 0; h < Hq; ++h)
-      for (int d = 0; d < kAttnD; ++d)
-        q[(static_cast<size_t>(b) * Hq + h) * kAttnD + d] =
-            static_cast<float>(attn_pat_q(b, h, d));
+  detail::attn_pattern_q(q.data(), B, Hq);
   p.upload_q_lens(q.data(), nullptr);
   const size_t groups = p.kv_elems() / 8;
   hipLaunchKernelGGL(attn_fill_kv_kernel, dim3(grid_for(groups)), dim3(kBlock), 0, 0,
@@ -653,28 +696,15 @@ inline AttnResult run_attn(int B = 32, int Hq = 64, int Hkv = 8, int L = 4096,
                      static_cast<int>(p.Lp), groups);
   HIP_CHECK(hipGetLastError());
   const float scale = detail::attn_default_scale();
-  p.launch(scale);  // warmup
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipDeviceSynchronize());
-  float ms = 0;
-  {
-    detail::Event t0, t1;
-    HIP_CHECK(hipEventRecord(t0.e, 0));
-    for (int i = 0; i < iters; ++i) p.launch(scale);
-    HIP_CHECK(hipEventRecord(t1.e, 0));
-    HIP_CHECK(hipEventSynchronize(t1.e));
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventElapsedTime(&ms, t0.e, t1.e));
-  }
+  const float ms = detail::time_launches(iters, [&p, scale] { p.launch(scale); });
   AttnResult r;
   const double sec = ms * 1e-3;
   r.steps_per_s = iters / sec;
   r.tok_per_s = r.steps_per_s * B;
   r.kv_gb_s = 2.0 * B * Hkv * static_cast<double>(L) * kAttnD * 2.0 * iters / sec / 1e9;
   std::vector<float> got(kAttnD), want(kAttnD);
-  const size_t rows = p.rows();
   for (int t = 0; t < 16; ++t) {
-    const size_t row = (static_cast<size_t>(t) * 1031 + 17) % rows;
+    const size_t row = detail::attn_spread_row(t, p.rows());
     HIP_CHECK(hipMemcpy(got.data(), p.dout.as<float>() + row * kAttnD,
                         kAttnD * sizeof(float), hipMemcpyDeviceToHost));
     detail::attn_pattern_row(want.data(), static_cast<int>(row / Hq),

@@ -250,6 +250,27 @@ struct Event {
   }
 };
 
+// Milliseconds of `iters` calls of launch() between two events, after one
+// warm-up call and a device synchronise: the timed loop of the GEMM and
+// attention payloads. run_membw_check and run_memcheck keep loops of their
+// own, on purpose: the first enqueues its check kernel behind the loop before
+// it synchronises, the second times two phases.
+template <class Launch>
+float time_launches(int iters, Launch&& launch) {
+  launch();  // warmup
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipDeviceSynchronize());
+  Event t0, t1;
+  HIP_CHECK(hipEventRecord(t0.e, 0));
+  for (int i = 0; i < iters; ++i) launch();
+  HIP_CHECK(hipEventRecord(t1.e, 0));
+  HIP_CHECK(hipEventSynchronize(t1.e));
+  HIP_CHECK(hipGetLastError());
+  float ms = 0;
+  HIP_CHECK(hipEventElapsedTime(&ms, t0.e, t1.e));
+  return ms;
+}
+
 constexpr size_t kGuardBytes = 4096;  // a multiple of 16: the interior stays aligned
 constexpr unsigned char kGuardByte = 0xA5;
 
@@ -550,7 +571,8 @@ inline int device_count() {
 
 }  // namespace payload
 
-// bf16 MFMA GEMM payload: uses HIP_CHECK, kBlock and the detail helpers from above
+// bf16 MFMA GEMM payload: uses HIP_CHECK, kBlock and the detail helpers from
+// above, detail::time_launches among them
 #include "payload_gemm.hpp"
 
 // MXFP8 block-scaled MFMA GEMM payload: same helpers, plus the gemm pattern
@@ -563,8 +585,12 @@ inline int device_count() {
 // memcheck payload: also uses grid_for
 #include "payload_memcheck.hpp"
 
-// decode attention payload: bf16x8, f32x4, to_bf16_rne and the detail helpers
+// decode attention payload: bf16x8, f32x4, to_bf16_rne and the detail helpers.
+// It also holds what both attention payloads share on the host: the common
+// shape limits (detail::AttnShape), the fp64 reference row, the check result
+// and its bound
 #include "payload_attn.hpp"
 
-// prefill attention payload: the decode one's head dim, patterns and scale
+// prefill attention payload: the decode one's head dim, patterns, scale and
+// shared host pieces
 #include "payload_prefill.hpp"

@@ -21,7 +21,7 @@
 // outside its buffers for any shape. Only the M x N region is copied back.
 //
 // Included by payload_core.hpp (needs its HIP_CHECK, kBlock, detail::DeviceBuffer
-// and detail::Event).
+// and detail::time_launches).
 
 #pragma once
 
@@ -160,7 +160,7 @@ struct GemmResult {
 
 namespace detail {
 
-// DeviceBuffer and Event are payload_core.hpp's
+// DeviceBuffer and time_launches are payload_core.hpp's
 
 inline size_t round_up(size_t v, size_t m) { return (v + m - 1) / m * m; }
 
@@ -298,19 +298,7 @@ double run_full_check(P& p, int device, PatternErr err) {
 template <class P>
 GemmResult run_timed(P& p, int iters, int device, PatternErr err) {
   p.upload(device);
-  p.launch();  // warmup
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipDeviceSynchronize());
-  float ms = 0;
-  {
-    Event t0, t1;
-    HIP_CHECK(hipEventRecord(t0.e, 0));
-    for (int i = 0; i < iters; ++i) p.launch();
-    HIP_CHECK(hipEventRecord(t1.e, 0));
-    HIP_CHECK(hipEventSynchronize(t1.e));
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventElapsedTime(&ms, t0.e, t1.e));
-  }
+  const float ms = time_launches(iters, [&p] { p.launch(); });
   GemmResult r;
   r.tflops = 2.0 * p.M * p.N * p.K * iters / (ms * 1e-3) / 1e12;
   for (int t = 0; t < 256; ++t) {

@@ -190,6 +190,42 @@ static void print_gemm_check(const GemmVerb& g, std::istringstream& iss) {
       err == 0.0 ? "true" : "false", g.name, m, n, k, json_num(err));
 }
 
+// the two attention payloads share their verbs' shape arguments and the head
+// of their report lines; a verb starts from its defaults
+struct AttnArgs {
+  int b, hq, hkv, len;
+
+  // <verb> [B HQ HKV L [...]]: all four or none
+  void parse(int argc, char** argv) {
+    if (argc > 5)
+      *this = {std::atoi(argv[2]), std::atoi(argv[3]), std::atoi(argv[4]),
+               std::atoi(argv[5])};
+  }
+
+  // serve's <verb> [B HQ HKV L]
+  void parse(std::istringstream& iss) {
+    int tb, tq, tk, tl;
+    if (iss >> tb >> tq >> tk >> tl) *this = {tb, tq, tk, tl};
+  }
+
+  void print_head(const char* cmd, bool ok) const {
+    std::printf(
+        "{\"ok\": %s, \"cmd\": \"%s\", \"batch\": %d, \"hq\": %d, \"hkv\": %d, "
+        "\"len\": %d, ",
+        ok ? "true" : "false", cmd, b, hq, hkv, len);
+  }
+};
+
+// serve's attn / prefill [B HQ HKV L]: the self-check at that shape; `extra`
+// goes between the head and the errors
+static void print_attn_check(const char* cmd, const AttnArgs& a, const AttnCheck& c,
+                             const char* extra) {
+  bool ok = c.max_err == 0.0 && c.max_rel <= kAttnRelBound;
+  a.print_head(cmd, ok);
+  std::printf("%s\"max_err\": %g, \"max_rel\": %g}\n", extra, json_num(c.max_err),
+              json_num(c.max_rel));
+}
+
 // one census run: the XCDs that ran a workgroup, and the per-XCD counts as the
 // elements of a JSON array
 struct Census {
@@ -249,44 +285,38 @@ int main(int argc, char** argv) {
     } else if (const GemmVerb* g = find_gemm_verb(cmd)) {
       return print_timed_gemm(*g, argc, argv) ? 0 : 1;
     } else if (std::strcmp(cmd, "attn") == 0) {
-      int b = argc > 5 ? std::atoi(argv[2]) : 32;
-      int hq = argc > 5 ? std::atoi(argv[3]) : 64;
-      int hkv = argc > 5 ? std::atoi(argv[4]) : 8;
-      int len = argc > 5 ? std::atoi(argv[5]) : 4096;
+      AttnArgs a{32, 64, 8, 4096};
+      a.parse(argc, argv);
       int iters = argc > 6 ? std::atoi(argv[6]) : 10;
       int splits = argc > 7 ? std::atoi(argv[7]) : 0;
       AttnCheck c = run_attn_check(2, 8, 2, 300);
-      AttnResult r = run_attn(b, hq, hkv, len, iters, 0, splits);
+      AttnResult r = run_attn(a.b, a.hq, a.hkv, a.len, iters, 0, splits);
       double max_err = r.max_err > c.max_err ? r.max_err : c.max_err;
       bool ok = max_err == 0.0 && c.max_rel <= kAttnRelBound;
+      a.print_head("attn", ok);
       std::printf(
-          "{\"ok\": %s, \"cmd\": \"attn\", \"batch\": %d, \"hq\": %d, "
-          "\"hkv\": %d, \"len\": %d, \"iters\": %d, \"kv_gb_per_s\": %.1f, "
-          "\"steps_per_s\": %.1f, \"tok_per_s\": %.1f, \"max_err\": %g, "
-          "\"max_rel\": %g}\n",
-          ok ? "true" : "false", b, hq, hkv, len, iters, r.kv_gb_s, r.steps_per_s,
-          r.tok_per_s, json_num(max_err), json_num(c.max_rel));
+          "\"iters\": %d, \"kv_gb_per_s\": %.1f, \"steps_per_s\": %.1f, "
+          "\"tok_per_s\": %.1f, \"max_err\": %g, \"max_rel\": %g}\n",
+          iters, r.kv_gb_s, r.steps_per_s, r.tok_per_s, json_num(max_err),
+          json_num(c.max_rel));
       return ok ? 0 : 1;
     } else if (std::strcmp(cmd, "prefill") == 0) {
-      int b = argc > 5 ? std::atoi(argv[2]) : 8;
-      int hq = argc > 5 ? std::atoi(argv[3]) : 64;
-      int hkv = argc > 5 ? std::atoi(argv[4]) : 8;
-      int len = argc > 5 ? std::atoi(argv[5]) : 4096;
+      AttnArgs a{8, 64, 8, 4096};
+      a.parse(argc, argv);
       int iters = argc > 6 ? std::atoi(argv[6]) : 10;
       bool causal = argc > 7 ? std::atoi(argv[7]) != 0 : true;
       int pattern = argc > 8 ? std::atoi(argv[8]) : kPrefillDense;
-      PrefillCheck c = run_prefill_check(2, 8, 2, 300, causal);
-      PrefillResult r = run_prefill(b, hq, hkv, len, iters, causal, 0, pattern);
+      AttnCheck c = run_prefill_check(2, 8, 2, 300, causal);
+      PrefillResult r = run_prefill(a.b, a.hq, a.hkv, a.len, iters, causal, 0, pattern);
       double max_rel = r.max_rel > c.max_rel ? r.max_rel : c.max_rel;
       if (std::isnan(r.max_rel) || std::isnan(c.max_rel)) max_rel = INFINITY;
-      bool ok = c.max_err == 0.0 && max_rel <= kPrefillRelBound;
+      bool ok = c.max_err == 0.0 && max_rel <= kAttnRelBound;
+      a.print_head("prefill", ok);
       std::printf(
-          "{\"ok\": %s, \"cmd\": \"prefill\", \"batch\": %d, \"hq\": %d, "
-          "\"hkv\": %d, \"len\": %d, \"iters\": %d, \"causal\": %s, "
-          "\"tflops\": %.2f, \"tok_per_s\": %.1f, \"max_err\": %g, "
-          "\"max_rel\": %g}\n",
-          ok ? "true" : "false", b, hq, hkv, len, iters, causal ? "true" : "false",
-          r.tflops, r.tok_per_s, json_num(c.max_err), json_num(max_rel));
+          "\"iters\": %d, \"causal\": %s, \"tflops\": %.2f, \"tok_per_s\": %.1f, "
+          "\"max_err\": %g, \"max_rel\": %g}\n",
+          iters, causal ? "true" : "false", r.tflops, r.tok_per_s, json_num(c.max_err),
+          json_num(max_rel));
       return ok ? 0 : 1;
     } else if (std::strcmp(cmd, "memcheck") == 0) {
       size_t bytes = argc > 2 ? std::strtoull(argv[2], nullptr, 10) : (size_t{1} << 30);
@@ -352,26 +382,14 @@ int main(int argc, char** argv) {
           } else if (const GemmVerb* g = find_gemm_verb(verb.c_str())) {
             print_gemm_check(*g, iss);
           } else if (verb == "attn") {
-            int b = 2, hq = 8, hkv = 2, len = 300, tb, tq, tk, tl;
-            if (iss >> tb >> tq >> tk >> tl) { b = tb; hq = tq; hkv = tk; len = tl; }
-            AttnCheck c = run_attn_check(b, hq, hkv, len);
-            bool ok = c.max_err == 0.0 && c.max_rel <= kAttnRelBound;
-            std::printf(
-                "{\"ok\": %s, \"cmd\": \"attn\", \"batch\": %d, \"hq\": %d, "
-                "\"hkv\": %d, \"len\": %d, \"max_err\": %g, \"max_rel\": %g}\n",
-                ok ? "true" : "false", b, hq, hkv, len, json_num(c.max_err),
-                json_num(c.max_rel));
+            AttnArgs a{2, 8, 2, 300};
+            a.parse(iss);
+            print_attn_check("attn", a, run_attn_check(a.b, a.hq, a.hkv, a.len), "");
           } else if (verb == "prefill") {
-            int b = 1, hq = 4, hkv = 2, len = 200, tb, tq, tk, tl;
-            if (iss >> tb >> tq >> tk >> tl) { b = tb; hq = tq; hkv = tk; len = tl; }
-            PrefillCheck c = run_prefill_check(b, hq, hkv, len);
-            bool ok = c.max_err == 0.0 && c.max_rel <= kPrefillRelBound;
-            std::printf(
-                "{\"ok\": %s, \"cmd\": \"prefill\", \"batch\": %d, \"hq\": %d, "
-                "\"hkv\": %d, \"len\": %d, \"causal\": true, \"max_err\": %g, "
-                "\"max_rel\": %g}\n",
-                ok ? "true" : "false", b, hq, hkv, len, json_num(c.max_err),
-                json_num(c.max_rel));
+            AttnArgs a{1, 4, 2, 200};
+            a.parse(iss);
+            print_attn_check("prefill", a, run_prefill_check(a.b, a.hq, a.hkv, a.len),
+                             "\"causal\": true, ");
           } else if (verb == "memcheck") {
             size_t bytes = size_t{64} << 20;
             iss >> bytes;

@@ -76,7 +76,9 @@
 // v_cvt_pk_bf16_f32, one ds_bpermute_b32. Measured: profiles/prefill_probe.md.
 //
 // Included by payload_core.hpp after payload_attn.hpp (needs kAttnD, its
-// pattern functions and default scale, and everything that header needs).
+// pattern functions, AttnCheck, kAttnRelBound, detail::AttnShape, attn_group,
+// attn_default_scale, attn_c2, attn_spread_row and attn_ref_row, and everything
+// that header needs).
 
 #pragma once
 
@@ -92,7 +94,6 @@ constexpr int kPrefillKeys = 64;      // keys per LDS tile
 constexpr int kPrefillWaveRows = 32;  // query rows per wave
 constexpr int kPrefillTileElems = kPrefillKeys * kAttnD;  // per tensor and tile
 constexpr int kPrefillMaxLen = 1 << 24;
-constexpr double kPrefillRelBound = 1.0 / 256;  // run_prefill_check's dense bound
 
 static_assert(kAttnD == 128, "the tile images are laid out for head dim 128");
 static_assert(kPrefillRows == (kBlock / 64) * kPrefillWaveRows, "one 32-row strip per wave");
@@ -444,43 +445,35 @@ __global__ __launch_bounds__(kBlock) void prefill_fill_kv_kernel(
 
 // ---- host layer ----------------------------------------------------------
 
-struct PrefillCheck {
-  double max_err = 0;  // selection pattern: expect exactly 0
-  double max_rel = 0;  // dense pattern: max |o - ref| / max |v|, <= 2^-8
-};
-
 struct PrefillResult {
   double tflops = 0;     // unmasked (q, k) pairs only
   double tok_per_s = 0;  // B L per launch
   double max_rel = 0;    // 16 spread rows against fp64
 };
 
+// The limits of the prefill payload, or std::invalid_argument; no HIP call.
+// There is no cap on Hq / Hkv, which it returns: every axis fits the kernel's
+// int arithmetic and the one-dimensional grid.
+inline int attn_prefill_shape(long long B, long long Hq, long long Hkv, long long L) {
+  const long long G = detail::attn_group("prefill", B, Hq, Hkv, L);
+  if (B > 65535 || Hq > 65535 || L > kPrefillMaxLen ||
+      B * Hq * ((L + kPrefillRows - 1) / kPrefillRows) > 0x7FFFFFFFll)
+    throw std::invalid_argument("prefill: shape too large");
+  return static_cast<int>(G);
+}
+
 namespace detail {
 
 // Shape, device buffers and launch of one prefill problem.
-struct PrefillProblem {
-  int B, Hq, Hkv, L, G;
+struct PrefillProblem : AttnShape {
   bool causal;
-  int device;
   size_t Lqp, Lkp;
   DeviceBuffer dq, dk, dvt, dout;
 
-  // There is no cap on Hq / Hkv. The limits: every axis fits the kernel's int
-  // arithmetic and the one-dimensional grid.
   PrefillProblem(int b, int hq, int hkv, int len, bool is_causal, int dev)
-      : B(b), Hq(hq), Hkv(hkv), L(len), causal(is_causal), device(dev) {
-    if (b < 1 || hq < 1 || hkv < 1 || len < 1)
-      throw std::invalid_argument("prefill: B, Hq, Hkv and L must be >= 1");
-    if (hq % hkv != 0)
-      throw std::invalid_argument("prefill: Hq must be a multiple of Hkv");
-    G = hq / hkv;
-    if (b > 65535 || hq > 65535 || len > kPrefillMaxLen)
-      throw std::invalid_argument("prefill: shape too large");
-    Lqp = round_up(len, kPrefillRows);
-    Lkp = round_up(len, kPrefillKeys);
-    if (static_cast<unsigned long long>(b) * hq * (Lqp / kPrefillRows) > 0x7FFFFFFFull)
-      throw std::invalid_argument("prefill: shape too large");
-  }
+      : AttnShape{b, hq, hkv, len, attn_prefill_shape(b, hq, hkv, len), dev},
+        causal(is_causal), Lqp(round_up(len, kPrefillRows)),
+        Lkp(round_up(len, kPrefillKeys)) {}
 
   size_t heads() const { return static_cast<size_t>(B) * Hq; }
   size_t q_elems() const { return heads() * Lqp * kAttnD; }
@@ -535,7 +528,7 @@ struct PrefillProblem {
   }
 
   void launch(float scale) const {
-    const float c2 = scale * 1.4426950408889634f;
+    const float c2 = attn_c2(scale);
     const unsigned grid = static_cast<unsigned>(heads() * (Lqp / kPrefillRows));
     hipLaunchKernelGGL(attn_prefill_kernel, dim3(grid), dim3(kBlock), 0, 0,
                        dq.as<const uint16_t>(), dk.as<const uint16_t>(),
@@ -556,29 +549,6 @@ struct PrefillProblem {
                           hipMemcpyDeviceToHost));
   }
 };
-
-// fp64 reference of output row (b, h, i) from the float tensors k and v of its
-// kv head (L x 128 each) and its q row; w is scratch of L doubles
-inline void prefill_ref_row(double* out, const float* qr, const float* kh,
-                            const float* vh, int i, int L, bool causal, double scale,
-                            std::vector<double>& w) {
-  const int n = causal ? i + 1 : L;
-  double mx = -INFINITY;
-  for (int t = 0; t < n; ++t) {
-    const float* kr = kh + static_cast<size_t>(t) * kAttnD;
-    double s = 0;
-    for (int d = 0; d < kAttnD; ++d) s += static_cast<double>(qr[d]) * kr[d];
-    w[t] = s * scale;
-    mx = std::max(mx, w[t]);
-  }
-  double den = 0;
-  for (int t = 0; t < n; ++t) den += (w[t] = std::exp(w[t] - mx));
-  for (int d = 0; d < kAttnD; ++d) {
-    double num = 0;
-    for (int t = 0; t < n; ++t) num += w[t] * vh[static_cast<size_t>(t) * kAttnD + d];
-    out[d] = num / den;
-  }
-}
 
 }  // namespace detail
 
@@ -601,8 +571,7 @@ inline void attn_prefill(const float* q, const float* k, const float* v, float* 
 // a row sees, divided by their count.
 inline void prefill_check_pattern(float* q, float* k, float* v, float* expected,
                                   int B, int Hq, int Hkv, int L, bool causal) {
-  detail::PrefillProblem shape(B, Hq, Hkv, L, causal, 0);  // validation only
-  const int G = shape.G;
+  const int G = attn_prefill_shape(B, Hq, Hkv, L);
   for (int b = 0; b < B; ++b) {
     for (int h = 0; h < Hq; ++h)
       for (int i = 0; i < L; ++i) {
@@ -649,14 +618,14 @@ inline void prefill_check_pattern(float* q, float* k, float* v, float* expected,
 // max_err, expect exactly 0. (b) the dense pattern against an fp64 reference:
 // max_rel = max |o - ref| / max |v|, expect <= 2^-8 by decode's derivation
 // (run_attn_check): the numerics are the same.
-inline PrefillCheck run_prefill_check(int B, int Hq, int Hkv, int L, bool causal = true,
-                                      int device = 0) {
-  detail::PrefillProblem shape(B, Hq, Hkv, L, causal, device);  // validate first
-  const size_t nq = shape.heads() * L * kAttnD;
+inline AttnCheck run_prefill_check(int B, int Hq, int Hkv, int L, bool causal = true,
+                                   int device = 0) {
+  const int G = attn_prefill_shape(B, Hq, Hkv, L);  // validate first
+  const size_t nq = static_cast<size_t>(B) * Hq * L * kAttnD;
   const size_t nkv = static_cast<size_t>(B) * Hkv * L * kAttnD;
   const float scale = detail::attn_default_scale();
   std::vector<float> q(nq), k(nkv), v(nkv), want(nq), got(nq);
-  PrefillCheck r;
+  AttnCheck r;
 
   prefill_check_pattern(q.data(), k.data(), v.data(), want.data(), B, Hq, Hkv, L, causal);
   attn_prefill(q.data(), k.data(), v.data(), got.data(), B, Hq, Hkv, L, causal, scale,
@@ -687,12 +656,12 @@ inline PrefillCheck run_prefill_check(int B, int Hq, int Hkv, int L, bool causal
   double max_abs = 0;
   for (int b = 0; b < B; ++b)
     for (int h = 0; h < Hq; ++h) {
-      const size_t bg = static_cast<size_t>(b) * Hkv + h / shape.G;
+      const size_t bg = static_cast<size_t>(b) * Hkv + h / G;
       for (int i = 0; i < L; ++i) {
         const size_t at = ((static_cast<size_t>(b) * Hq + h) * L + i) * kAttnD;
-        detail::prefill_ref_row(ref.data(), q.data() + at, k.data() + bg * L * kAttnD,
-                                v.data() + bg * L * kAttnD, i, L, causal,
-                                static_cast<double>(scale), w);
+        detail::attn_ref_row(ref.data(), q.data() + at, k.data() + bg * L * kAttnD,
+                             v.data() + bg * L * kAttnD, causal ? i + 1 : L,
+                             static_cast<double>(scale), w);
         for (int d = 0; d < kAttnD; ++d)
           detail::note_err(max_abs, std::fabs(static_cast<double>(got[at + d]) - ref[d]));
       }
@@ -720,19 +689,7 @@ inline PrefillResult run_prefill(int B = 8, int Hq = 64, int Hkv = 8, int L = 40
   p.alloc();
   p.fill(pattern);
   const float scale = detail::attn_default_scale();
-  p.launch(scale);  // warmup
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipDeviceSynchronize());
-  float ms = 0;
-  {
-    detail::Event t0, t1;
-    HIP_CHECK(hipEventRecord(t0.e, 0));
-    for (int i = 0; i < iters; ++i) p.launch(scale);
-    HIP_CHECK(hipEventRecord(t1.e, 0));
-    HIP_CHECK(hipEventSynchronize(t1.e));
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventElapsedTime(&ms, t0.e, t1.e));
-  }
+  const float ms = detail::time_launches(iters, [&p, scale] { p.launch(scale); });
   PrefillResult r;
   const double sec = ms * 1e-3;
   const double pairs = causal ? static_cast<double>(L) * (L + 1.0) / 2.0
@@ -745,7 +702,7 @@ inline PrefillResult run_prefill(int B = 8, int Hq = 64, int Hkv = 8, int L = 40
   std::vector<double> w(L), ref(kAttnD);
   double max_abs = 0, vmax = 0;
   for (int t = 0; t < 16; ++t) {
-    const size_t bh = (static_cast<size_t>(t) * 1031 + 17) % p.heads();
+    const size_t bh = detail::attn_spread_row(t, p.heads());
     const int b = static_cast<int>(bh / Hq), h = static_cast<int>(bh % Hq), g = h / p.G;
     const int i = static_cast<int>(static_cast<long long>(t) * (L - 1) / 15);
     const int n = causal ? i + 1 : L;
@@ -757,8 +714,8 @@ inline PrefillResult run_prefill(int B = 8, int Hq = 64, int Hkv = 8, int L = 40
         vh[at] = prefill_elem(pattern, 3, Hkv, L, b, g, u, d);
         vmax = std::max(vmax, std::fabs(static_cast<double>(vh[at])));
       }
-    detail::prefill_ref_row(ref.data(), qr.data(), kh.data(), vh.data(), i, L, causal,
-                            static_cast<double>(scale), w);
+    detail::attn_ref_row(ref.data(), qr.data(), kh.data(), vh.data(), n,
+                         static_cast<double>(scale), w);
     HIP_CHECK(hipMemcpy(got.data(), p.dout.as<float>() + (bh * p.Lqp + i) * kAttnD,
                         kAttnD * sizeof(float), hipMemcpyDeviceToHost));
     for (int d = 0; d < kAttnD; ++d)

@@ -209,6 +209,36 @@ void attn_finite(const char* who, const f32_array& q, const f32_array& k,
       throw py::value_error(std::string(who) + ": k or v has a non-finite element");
 }
 
+// (q, k, v, expected) of one of the selection patterns: q and expected of
+// q_shape, k and v (B,Hkv,L,128), filled by fill(q, k, v, expected)
+template <class Fill>
+py::tuple attn_pattern_arrays(const std::vector<py::ssize_t>& q_shape, py::ssize_t B,
+                              py::ssize_t Hkv, py::ssize_t L, Fill fill) {
+  const std::vector<py::ssize_t> kv_shape{B, Hkv, L, payload::kAttnD};
+  py::array_t<float> q(q_shape), e(q_shape), k(kv_shape), v(kv_shape);
+  fill(q.mutable_data(), k.mutable_data(), v.mutable_data(), e.mutable_data());
+  return py::make_tuple(q, k, v, e);
+}
+
+// the report of one of the attention self-checks
+py::dict attn_check_dict(const payload::AttnCheck& r) {
+  py::dict d;
+  d["max_err"] = r.max_err;
+  d["max_rel"] = r.max_rel;
+  return d;
+}
+
+// the shape keys that head the report of one of the timed attention runs
+py::dict attn_timed_dict(int batch, int hq, int hkv, int length, int iters) {
+  py::dict d;
+  d["batch"] = batch;
+  d["hq"] = hq;
+  d["hkv"] = hkv;
+  d["len"] = length;
+  d["iters"] = iters;
+  return d;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_payload, m) {
@@ -635,32 +665,19 @@ PYBIND11_MODULE(_payload, m) {
     return lens;
   };
 
-  // batch, hq, hkv, length of a decode problem, or ValueError
-  auto attn_shape = [](const char* who, py::ssize_t B, py::ssize_t Hq,
-                       py::ssize_t Hkv, py::ssize_t L, int splits) {
-    std::string w(who);
-    if (B < 1 || Hq < 1 || Hkv < 1 || L < 1)
-      throw py::value_error(w + ": empty axis");
-    if (B > 65535 || Hkv > 65535 || Hq > 65535 * 16 || L > (1 << 28))
-      throw py::value_error(w + ": shape too large");
-    if (Hq % Hkv != 0)
-      throw py::value_error(w + ": Hq must be a multiple of Hkv");
-    if (Hq / Hkv > payload::kAttnMaxGroup)
-      throw py::value_error(w + ": Hq / Hkv must be <= 16");
-    if (splits < 0 || splits > payload::kAttnMaxSplits)
-      throw py::value_error(w + ": splits must be in 0 .. 64");
-  };
+  // A shape's limits are the headers': attn_decode_shape and attn_prefill_shape
+  // throw std::invalid_argument, which pybind11 raises as ValueError. Every
+  // entry calls its check first, before it allocates or releases the GIL.
 
   m.def(
       "attn_decode",
-      [attn_lengths, attn_shape](f32_array q, f32_array k, f32_array v,
-                                 py::object lengths, py::object scale, int splits,
-                                 int device) {
+      [attn_lengths](f32_array q, f32_array k, f32_array v, py::object lengths,
+                     py::object scale, int splits, int device) {
         const char* who = "attn_decode";
         attn_operands(who, q, 3, "(B,Hq,128)", k, v);
         const py::ssize_t B = q.shape(0), Hq = q.shape(1), Hkv = k.shape(1),
                           L = k.shape(2);
-        attn_shape(who, B, Hq, Hkv, L, splits);
+        payload::attn_decode_shape(B, Hq, Hkv, L, splits);
         std::vector<int> lens = attn_lengths(who, lengths, B, L);
         const float sc = attn_scale(who, scale);
         attn_finite(who, q, k, v);
@@ -688,21 +705,15 @@ PYBIND11_MODULE(_payload, m) {
 
   m.def(
       "attn_check_pattern",
-      [attn_lengths, attn_shape](int batch, int hq, int hkv, int length,
-                                 py::object lengths) {
-        attn_shape("attn_check_pattern", batch, hq, hkv, length, 0);
+      [attn_lengths](int batch, int hq, int hkv, int length, py::object lengths) {
+        payload::attn_decode_shape(batch, hq, hkv, length);
         std::vector<int> lens = attn_lengths("attn_check_pattern", lengths, batch, length);
-        const py::ssize_t D = payload::kAttnD;
-        py::array_t<float> q({static_cast<py::ssize_t>(batch), static_cast<py::ssize_t>(hq), D});
-        py::array_t<float> e({static_cast<py::ssize_t>(batch), static_cast<py::ssize_t>(hq), D});
-        py::array_t<float> k({static_cast<py::ssize_t>(batch), static_cast<py::ssize_t>(hkv),
-                              static_cast<py::ssize_t>(length), D});
-        py::array_t<float> v({static_cast<py::ssize_t>(batch), static_cast<py::ssize_t>(hkv),
-                              static_cast<py::ssize_t>(length), D});
-        payload::attn_check_pattern(q.mutable_data(), k.mutable_data(),
-                                    v.mutable_data(), e.mutable_data(), batch, hq, hkv,
-                                    length, lens.empty() ? nullptr : lens.data());
-        return py::make_tuple(q, k, v, e);
+        return attn_pattern_arrays(
+            {batch, hq, payload::kAttnD}, batch, hkv, length,
+            [&](float* q, float* k, float* v, float* e) {
+              payload::attn_check_pattern(q, k, v, e, batch, hq, hkv, length,
+                                          lens.empty() ? nullptr : lens.data());
+            });
       },
       py::arg("batch"), py::arg("hq"), py::arg("hkv"), py::arg("length"),
       py::arg("lengths") = py::none(),
@@ -713,17 +724,14 @@ PYBIND11_MODULE(_payload, m) {
 
   m.def(
       "run_attn_check",
-      [attn_shape](int batch, int hq, int hkv, int length, int splits, int device) {
-        attn_shape("run_attn_check", batch, hq, hkv, length, splits);
+      [](int batch, int hq, int hkv, int length, int splits, int device) {
+        payload::attn_decode_shape(batch, hq, hkv, length, splits);
         payload::AttnCheck r;
         {
           py::gil_scoped_release rel;
           r = payload::run_attn_check(batch, hq, hkv, length, splits, device);
         }
-        py::dict d;
-        d["max_err"] = r.max_err;
-        d["max_rel"] = r.max_rel;
-        return d;
+        return attn_check_dict(r);
       },
       py::arg("batch"), py::arg("hq"), py::arg("hkv"), py::arg("length"),
       py::arg("splits") = 0, py::arg("device") = 0,
@@ -733,20 +741,14 @@ PYBIND11_MODULE(_payload, m) {
 
   m.def(
       "run_attn",
-      [attn_shape](int batch, int hq, int hkv, int length, int iters, int device) {
-        attn_shape("run_attn", batch, hq, hkv, length, 0);
-        if (iters < 1) throw py::value_error("run_attn: iters must be >= 1");
+      [](int batch, int hq, int hkv, int length, int iters, int device) {
+        payload::attn_decode_shape(batch, hq, hkv, length);
         payload::AttnResult r;
         {
           py::gil_scoped_release rel;
           r = payload::run_attn(batch, hq, hkv, length, iters, device);
         }
-        py::dict d;
-        d["batch"] = batch;
-        d["hq"] = hq;
-        d["hkv"] = hkv;
-        d["len"] = length;
-        d["iters"] = iters;
+        py::dict d = attn_timed_dict(batch, hq, hkv, length, iters);
         d["kv_gb_per_s"] = r.kv_gb_s;
         d["steps_per_s"] = r.steps_per_s;
         d["tok_per_s"] = r.tok_per_s;
@@ -763,35 +765,17 @@ PYBIND11_MODULE(_payload, m) {
   m.attr("PREFILL_ROWS") = payload::kPrefillRows;
   m.attr("PREFILL_KEYS") = payload::kPrefillKeys;
 
-  // batch, hq, hkv, length of a prefill problem, or ValueError: the limits of
-  // detail::PrefillProblem, checked here before any HIP call
-  auto prefill_shape = [](const char* who, py::ssize_t B, py::ssize_t Hq,
-                          py::ssize_t Hkv, py::ssize_t L) {
-    std::string w(who);
-    if (B < 1 || Hq < 1 || Hkv < 1 || L < 1)
-      throw py::value_error(w + ": empty axis");
-    if (B > 65535 || Hq > 65535 || Hkv > 65535 || L > payload::kPrefillMaxLen)
-      throw py::value_error(w + ": shape too large");
-    if (Hq % Hkv != 0)
-      throw py::value_error(w + ": Hq must be a multiple of Hkv");
-    const unsigned long long blocks =
-        (static_cast<unsigned long long>(L) + payload::kPrefillRows - 1) /
-        payload::kPrefillRows;
-    if (static_cast<unsigned long long>(B) * Hq * blocks > 0x7FFFFFFFull)
-      throw py::value_error(w + ": shape too large");
-  };
-
   m.def(
       "attn_prefill",
-      [prefill_shape](f32_array q, f32_array k, f32_array v, bool causal,
-                      py::object scale, int device) {
+      [](f32_array q, f32_array k, f32_array v, bool causal, py::object scale,
+         int device) {
         const char* who = "attn_prefill";
         attn_operands(who, q, 4, "(B,Hq,L,128)", k, v);
         if (k.shape(2) != q.shape(2))
           throw py::value_error("attn_prefill: q and k differ in length");
         const py::ssize_t B = q.shape(0), Hq = q.shape(1), Hkv = k.shape(1),
                           L = q.shape(2);
-        prefill_shape(who, B, Hq, Hkv, L);
+        payload::attn_prefill_shape(B, Hq, Hkv, L);
         const float sc = attn_scale(who, scale);
         attn_finite(who, q, k, v);
         const float* pq = q.data();
@@ -817,17 +801,13 @@ PYBIND11_MODULE(_payload, m) {
 
   m.def(
       "prefill_check_pattern",
-      [prefill_shape](int batch, int hq, int hkv, int length, bool causal) {
-        prefill_shape("prefill_check_pattern", batch, hq, hkv, length);
-        const py::ssize_t D = payload::kAttnD, B = batch, L = length;
-        py::array_t<float> q({B, static_cast<py::ssize_t>(hq), L, D});
-        py::array_t<float> e({B, static_cast<py::ssize_t>(hq), L, D});
-        py::array_t<float> k({B, static_cast<py::ssize_t>(hkv), L, D});
-        py::array_t<float> v({B, static_cast<py::ssize_t>(hkv), L, D});
-        payload::prefill_check_pattern(q.mutable_data(), k.mutable_data(),
-                                       v.mutable_data(), e.mutable_data(), batch, hq,
-                                       hkv, length, causal);
-        return py::make_tuple(q, k, v, e);
+      [](int batch, int hq, int hkv, int length, bool causal) {
+        payload::attn_prefill_shape(batch, hq, hkv, length);
+        return attn_pattern_arrays(
+            {batch, hq, length, payload::kAttnD}, batch, hkv, length,
+            [&](float* q, float* k, float* v, float* e) {
+              payload::prefill_check_pattern(q, k, v, e, batch, hq, hkv, length, causal);
+            });
       },
       py::arg("batch"), py::arg("hq"), py::arg("hkv"), py::arg("length"),
       py::arg("causal") = true,
@@ -838,17 +818,14 @@ PYBIND11_MODULE(_payload, m) {
 
   m.def(
       "run_prefill_check",
-      [prefill_shape](int batch, int hq, int hkv, int length, bool causal, int device) {
-        prefill_shape("run_prefill_check", batch, hq, hkv, length);
-        payload::PrefillCheck r;
+      [](int batch, int hq, int hkv, int length, bool causal, int device) {
+        payload::attn_prefill_shape(batch, hq, hkv, length);
+        payload::AttnCheck r;
         {
           py::gil_scoped_release rel;
           r = payload::run_prefill_check(batch, hq, hkv, length, causal, device);
         }
-        py::dict d;
-        d["max_err"] = r.max_err;
-        d["max_rel"] = r.max_rel;
-        return d;
+        return attn_check_dict(r);
       },
       py::arg("batch"), py::arg("hq"), py::arg("hkv"), py::arg("length"),
       py::arg("causal") = true, py::arg("device") = 0,
@@ -858,24 +835,16 @@ PYBIND11_MODULE(_payload, m) {
 
   m.def(
       "run_prefill",
-      [prefill_shape](int batch, int hq, int hkv, int length, int iters, bool causal,
-                      int device, int pattern) {
-        prefill_shape("run_prefill", batch, hq, hkv, length);
-        if (iters < 1) throw py::value_error("run_prefill: iters must be >= 1");
-        if (pattern != payload::kPrefillDense && pattern != payload::kPrefillSelection)
-          throw py::value_error("run_prefill: pattern must be 0 (dense) or 1 (selection)");
+      [](int batch, int hq, int hkv, int length, int iters, bool causal, int device,
+         int pattern) {
+        payload::attn_prefill_shape(batch, hq, hkv, length);
         payload::PrefillResult r;
         {
           py::gil_scoped_release rel;
           r = payload::run_prefill(batch, hq, hkv, length, iters, causal, device,
                                    pattern);
         }
-        py::dict d;
-        d["batch"] = batch;
-        d["hq"] = hq;
-        d["hkv"] = hkv;
-        d["len"] = length;
-        d["iters"] = iters;
+        py::dict d = attn_timed_dict(batch, hq, hkv, length, iters);
         d["causal"] = causal;
         d["tflops"] = r.tflops;
         d["tok_per_s"] = r.tok_per_s;

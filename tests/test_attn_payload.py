@@ -185,6 +185,22 @@ def test_attn_decode_rejects_bad_arguments(payload):
         payload.run_attn(1, 2, 1, 8, iters=0)
 
 
+# too many sequences, too many kv heads, too long a cache
+TOO_LARGE_SHAPES = [(70000, 4, 4, 8), (1, 70000 * 16, 70000, 8),
+                    (1, 4, 4, 2 ** 28 + 1)]
+
+
+@pytest.mark.parametrize("shape", TOO_LARGE_SHAPES)
+def test_attn_rejects_too_large_shapes(payload, shape):
+    # at once: the last shape would otherwise ask for tens of GiB
+    with pytest.raises(ValueError):
+        payload.attn_check_pattern(*shape)
+    with pytest.raises(ValueError):
+        payload.run_attn_check(*shape)
+    with pytest.raises(ValueError):
+        payload.run_attn(*shape)
+
+
 # ---- CPU: judge_attn --------------------------------------------------------
 
 def report(**over):
