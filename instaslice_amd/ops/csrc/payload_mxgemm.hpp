@@ -1,48 +1,66 @@
-// gfx950 MXFP8 block-scaled matrix-core GEMM payload.
+// gfx950 MX block-scaled matrix-core GEMM kernel, and the MXFP8 payload on it.
 //
-// gemm proves the bf16 MFMA path; this one proves the low-precision path a
-// tenant of an MI355X pays for. On gfx950 the fp8 peak is reached only through
-// the block-scaled instruction v_mfma_scale_f32_16x16x128_f8f6f4 (twice the
-// bf16 rate per clock); the plain _fp8_fp8 forms run at the bf16 rate.
+// gemm proves the bf16 MFMA path; the MX payloads prove the low-precision paths
+// a tenant of an MI355X pays for. On gfx950 the fp8 and fp4 peaks are reached
+// only through the block-scaled instruction v_mfma_scale_f32_16x16x128_f8f6f4
+// (e4m3: twice the bf16 rate per clock, e2m1: four times); the plain _fp8_fp8
+// forms run at the bf16 rate.
 //
 //   C[M,N] (fp32) = sum_k A[i,k] * 2^(sa[i,k/32]-127) * B[k,j] * 2^(sb[k/32,j]-127)
 //
-// A and B are OCP e4m3fn bytes (not the MI300 fnuz encoding), sa and sb E8M0
-// bytes, one per 32 consecutive K elements of a row of A or a column of B (the
-// OCP MX block).
+// sa and sb are E8M0 bytes, one per 32 consecutive K elements of a row of A or
+// a column of B (the OCP MX block). For this payload A and B are OCP e4m3fn
+// bytes (not the MI300 fnuz encoding); payload_mxfp4.hpp has the e2m1 elements.
 //
-//   block tile   128 x 128, K-step 128, 256 threads (4 wave64s as 2 x 2)
+// One kernel template, gemm_mx_kernel<kSel>, serves both formats. kSel is the
+// instruction's format selector (cbsz = blgp): 0 for e4m3, 4 for e2m1. What is
+// the same for both:
+//
+//   block tile   128 x 128, 256 threads (4 wave64s as 2 x 2)
 //   wave tile    64 x 64 = 4 x 4 MFMA tiles of 16 x 16 (64 accumulator VGPRs)
+//   K-step       128 bytes of every row: 128 e4m3 or 256 e2m1 elements
 //   staging      as gemm_bf16_kernel: 16-byte global loads -> registers ->
 //                ds_write_b128 into one LDS buffer per operand; the loads for
 //                K-step t+1 are issued before the MFMAs of step t
-//   fragment     measured on the hardware with one-hot operands and per-block
-//                scales (tests/test_mxgemm_payload.py pins it): lane l holds
-//                row/col l & 15; its registers 0-3 hold the 16 consecutive k
-//                16 (l >> 4) .. +15 and its registers 4-7 the 16 consecutive k
-//                64 + 16 (l >> 4) .. +15, two ds_read_b128. The scale of MX
-//                block kb (k = 32 kb .. +31) of row/col r is taken from lane
-//                16 kb + r, byte OPSEL of its scale register. So the lane
-//                quarter l >> 4 supplies the scale of block l >> 4 although it
-//                holds half of two other blocks' elements. (The 32-consecutive-k
-//                map that composable-kernel's headers describe gives wrong
-//                sums as soon as the scales of a row differ.)
 //   LDS image    [128 rows][128 bytes], the 16-byte slot index XORed with
-//                (row >> 1) & 7 as in the bf16 kernel. Register half h of lane
-//                quarter q reads slot 4 h + q: the read pattern of the bf16
-//                kernel's K-substep h, conflict-free for the same reason.
-//   scales       one dword per lane, operand and K-step: its four bytes are
-//                the scales of the lane's block (l >> 4) for rows l & 15 of
-//                the wave's four MFMA tiles, and OPSEL = tile index picks the
+//                (row >> 1) & 7 as in the bf16 kernel (mx_lds_off). A lane of
+//                quarter q = l >> 4 reads slot 4 h + q, h = 0 or 1: the read
+//                pattern of the bf16 kernel's K-substep h, conflict-free for
+//                the same reason.
+//   lane map     measured on the hardware with one-hot operands and per-block
+//                scales (the K-order and scale-block tests of both formats pin
+//                it): lane l holds row/col l & 15, and the scale of MX block
+//                kb (k = 32 kb .. +31 of the instruction's 128) of row/col r
+//                is taken from lane 16 kb + r, byte OPSEL of its scale
+//                register.
+//   scales       one dword per lane, operand and MFMA: its four bytes are the
+//                scales of the lane's block (l >> 4) for rows l & 15 of the
+//                wave's four MFMA tiles, and OPSEL = tile index picks the
 //                byte. The host lays the Mp x Kp/32 scale bytes out for that
-//                (mx_scale_off): [64-row group][K-step][lane][tile], so a wave
-//                reads 256 contiguous bytes per operand and K-step, one K-step
-//                ahead like the tiles. Loading a byte per fragment instead
-//                (eight byte loads per lane and K-step) halved the rate.
+//                (mx_scale_off): [64-row group][128 k][lane][tile], so a wave
+//                reads 256 contiguous bytes per operand and MFMA of a K-step,
+//                one K-step ahead like the tiles. Loading a byte per fragment
+//                instead (eight byte loads per lane and K-step) halved the
+//                e4m3 rate.
 //
-// The host stores B transposed (N x K, K-contiguous), zero-pads M, N and K to
-// 128 and pads the scale arrays to match with 127 (2^0): the kernel has no edge
-// branch and forms no address outside its buffers for any shape.
+// What differs (mx_frag, mx_mfma and kSubs below):
+//
+//   e4m3   one MFMA per K-step. Registers 0-3 of lane l hold the 16 consecutive
+//          k 16 (l >> 4) .. +15 and registers 4-7 the 16 consecutive k
+//          64 + 16 (l >> 4) .. +15: slots (l >> 4) and 4 + (l >> 4) of the
+//          row, two ds_read_b128. So the lane quarter l >> 4 supplies the
+//          scale of block l >> 4 although it holds half of two other blocks'
+//          elements. (The 32-consecutive-k map that composable-kernel's
+//          headers describe gives wrong sums as soon as the scales of a row
+//          differ.)
+//   e2m1   two MFMAs per K-step, sub-steps s = 0, 1 of 128 elements. Sub-step s
+//          reads slot 4 s + (l >> 4), one ds_read_b128, into registers 0-3;
+//          registers 4-7 are zeros (payload_mxfp4.hpp has the measured facts).
+//
+// The host stores B transposed (N x K, K-contiguous), zero-pads M and N to 128
+// and K to a K-step and pads the scale arrays to match with 127 (2^0): the
+// kernel has no edge branch and forms no address outside its buffers for any
+// shape.
 //
 // When both scale operands of the builtin are the compile-time constant 0 the
 // compiler emits the unscaled v_mfma_f32_16x16x128_f8f6f4; a scale of 1.0 is
@@ -60,12 +78,12 @@
 
 namespace payload {
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));  // 16 fp8, 4 VGPRs
-typedef int i32x8 __attribute__((ext_vector_type(8)));  // 32 fp8, 8 VGPRs
+typedef int i32x4 __attribute__((ext_vector_type(4)));  // 16 staged bytes, 4 VGPRs
+typedef int i32x8 __attribute__((ext_vector_type(8)));  // an MFMA operand, 8 VGPRs
 
 constexpr int kMxBM = 128;
 constexpr int kMxBN = 128;
-constexpr int kMxBK = 128;   // fp8 elements = bytes per row of a K-step
+constexpr int kMxBK = 128;   // bytes per row of a K-step; elements per MFMA
 constexpr int kMxBlock = 32;  // elements per scale (the OCP MX block)
 constexpr int kMxSlots = kMxBK / 16;                 // 16-byte slots per row
 constexpr int kMxLoads = kMxBM * kMxSlots / kBlock;  // per thread per operand
@@ -96,21 +114,39 @@ __host__ __device__ inline size_t mx_scale_off(size_t row, size_t kb, size_t Kb)
   return ((g * (Kb / 4) + t) * 64 + fq * 16 + fr) * 4 + m;
 }
 
-// cbsz = blgp = 0: e4m3 operands. OA / OB pick the byte of sa / sb that holds
-// the scale (the builtin wants them as constants).
-template <int OA, int OB>
-__device__ __forceinline__ f32x4 mx_mfma(i32x8 a, i32x8 b, f32x4 c, int sa, int sb) {
-  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, OA, sa,
-                                                          OB, sb);
+// the operand of lane (row, fq) for MFMA s of the K-step staged in `tile`
+template <int kSel>
+__device__ __forceinline__ i32x8 mx_frag(const uint8_t* tile, int row, int fq, int s) {
+  if constexpr (kSel == 0) {
+    i32x4 lo = *reinterpret_cast<const i32x4*>(tile + mx_lds_off(row, fq));
+    i32x4 hi = *reinterpret_cast<const i32x4*>(tile + mx_lds_off(row, 4 + fq));
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+  } else {
+    i32x4 v = *reinterpret_cast<const i32x4*>(tile + mx_lds_off(row, 4 * s + fq));
+    return i32x8{v[0], v[1], v[2], v[3], 0, 0, 0, 0};  // the compiler drops 4-7
+  }
 }
 
-// a: Mp x Kp, bt: Np x Kp (B transposed), sa, sbt: scale images of Mp x Kp/32
-// and Np x Kp/32 bytes (mx_scale_off), c: Mp x Np; Mp, Np and Kp multiples of
-// 128. grid = (Np / 128, Mp / 128).
-__global__ __launch_bounds__(kBlock) void gemm_mxfp8_kernel(
+// OA / OB pick the byte of sa / sb that holds the scale (the builtin wants them
+// as constants).
+template <int kSel, int OA, int OB>
+__device__ __forceinline__ f32x4 mx_mfma(i32x8 a, i32x8 b, f32x4 c, int sa, int sb) {
+  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, kSel, kSel, OA,
+                                                          sa, OB, sb);
+}
+
+// a: Mp rows, bt: Np rows (B transposed) of Kp elements, one (e4m3) or two
+// (e2m1) to a byte; sa, sbt: scale images of Mp x Kp/32 and Np x Kp/32 bytes
+// (mx_scale_off); c: Mp x Np. Mp and Np are multiples of 128 and a row a
+// multiple of 128 bytes. grid = (Np / 128, Mp / 128).
+template <int kSel>
+__global__ __launch_bounds__(kBlock) void gemm_mx_kernel(
     const uint8_t* __restrict__ a, const uint8_t* __restrict__ bt,
     const uint8_t* __restrict__ sa, const uint8_t* __restrict__ sbt,
     float* __restrict__ c, int Np, int Kp) {
+  static_assert(kSel == 0 || kSel == 4, "e4m3 or e2m1");
+  constexpr int kSubs = kSel == 4 ? 2 : 1;  // MFMAs per K-step = elements per byte
+
   __shared__ __attribute__((aligned(16))) uint8_t lds[(kMxBM + kMxBN) * kMxBK];
   uint8_t* lds_a = lds;
   uint8_t* lds_b = lds + kMxBM * kMxBK;
@@ -125,25 +161,31 @@ __global__ __launch_bounds__(kBlock) void gemm_mxfp8_kernel(
   const int srow = tid >> 3, sslot = tid & 7;
   const size_t brow = static_cast<size_t>(blockIdx.y) * kMxBM;
   const size_t bcol = static_cast<size_t>(blockIdx.x) * kMxBN;
+  const int Kbytes = Kp >> (kSubs - 1);  // bytes per row
   // block-uniform bases plus 32-bit lane offsets shared by both operands
-  // (128 Kp < 2^32: the host limits Kp): fewer address registers
-  const uint8_t* ga = a + brow * Kp;
-  const uint8_t* gb = bt + bcol * Kp;
+  // (128 Kbytes < 2^32: the host limits Kp): fewer address registers
+  const uint8_t* ga = a + brow * Kbytes;
+  const uint8_t* gb = bt + bcol * Kbytes;
   unsigned soff[kMxLoads];
 #pragma unroll
   for (int i = 0; i < kMxLoads; ++i)
     soff[i] = static_cast<unsigned>(srow + i * (kBlock / kMxSlots)) *
-                  static_cast<unsigned>(Kp) + sslot * 16;
+                  static_cast<unsigned>(Kbytes) + sslot * 16;
 
-  // the lane's scale dword of K-step t: 64 dwords per wave tile and K-step
-  const size_t steps = static_cast<size_t>(Kp / kMxBK);
+  // the lane's scale dwords: 64 dwords per wave tile and MFMA of a row
+  const size_t mfmas = static_cast<size_t>(Kp / kMxBK);
   const int* gsa = reinterpret_cast<const int*>(sa) +
-                   (brow / 64 + wr) * steps * 64 + lane;
+                   (brow / 64 + wr) * mfmas * 64 + lane;
   const int* gsb = reinterpret_cast<const int*>(sbt) +
-                   (bcol / 64 + wc) * steps * 64 + lane;
+                   (bcol / 64 + wc) * mfmas * 64 + lane;
 
   i32x4 ra[kMxLoads], rb[kMxLoads];
-  int nsa = gsa[0], nsb = gsb[0];
+  int nsa[kSubs], nsb[kSubs];
+#pragma unroll
+  for (int s = 0; s < kSubs; ++s) {
+    nsa[s] = gsa[64 * s];
+    nsb[s] = gsb[64 * s];
+  }
 #pragma unroll
   for (int i = 0; i < kMxLoads; ++i) {
     ra[i] = *reinterpret_cast<const i32x4*>(ga + soff[i]);
@@ -156,54 +198,57 @@ __global__ __launch_bounds__(kBlock) void gemm_mxfp8_kernel(
 #pragma unroll
     for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  for (int k0 = 0; k0 < Kp; k0 += kMxBK) {
+  // b0: byte offset of the K-step in a row
+  for (int b0 = 0; b0 < Kbytes; b0 += kMxBK) {
 #pragma unroll
     for (int i = 0; i < kMxLoads; ++i) {
       int row = srow + i * (kBlock / kMxSlots);
       *reinterpret_cast<i32x4*>(lds_a + mx_lds_off(row, sslot)) = ra[i];
       *reinterpret_cast<i32x4*>(lds_b + mx_lds_off(row, sslot)) = rb[i];
     }
-    const int sca = nsa, scb = nsb;
+    int sca[kSubs], scb[kSubs];
+#pragma unroll
+    for (int s = 0; s < kSubs; ++s) {
+      sca[s] = nsa[s];
+      scb[s] = nsb[s];
+    }
     __syncthreads();
 
-    if (k0 + kMxBK < Kp) {  // block-uniform: prefetch the next K-step
+    if (b0 + kMxBK < Kbytes) {  // block-uniform: prefetch the next K-step
 #pragma unroll
       for (int i = 0; i < kMxLoads; ++i) {
-        ra[i] = *reinterpret_cast<const i32x4*>(ga + k0 + kMxBK + soff[i]);
-        rb[i] = *reinterpret_cast<const i32x4*>(gb + k0 + kMxBK + soff[i]);
+        ra[i] = *reinterpret_cast<const i32x4*>(ga + b0 + kMxBK + soff[i]);
+        rb[i] = *reinterpret_cast<const i32x4*>(gb + b0 + kMxBK + soff[i]);
       }
-      const int next = (k0 + kMxBK) / kMxBK * 64;
-      nsa = gsa[next];
-      nsb = gsb[next];
+      const int next = (b0 + kMxBK) / kMxBK * 64 * kSubs;
+#pragma unroll
+      for (int s = 0; s < kSubs; ++s) {
+        nsa[s] = gsa[next + 64 * s];
+        nsb[s] = gsb[next + 64 * s];
+      }
     }
 
-    // lane l, register half h: A[row l&15][k = 64h + 16(l>>4) + j] and
-    // B[k = 64h + 16(l>>4) + j][col l&15], j = 0..15: slots (l>>4) and
-    // 4 + (l>>4) of the row
-    i32x8 fb[4];
 #pragma unroll
-    for (int n = 0; n < 4; ++n) {
-      int row = wc * 64 + n * 16 + fr;
-      i32x4 lo = *reinterpret_cast<const i32x4*>(lds_b + mx_lds_off(row, fq));
-      i32x4 hi = *reinterpret_cast<const i32x4*>(lds_b + mx_lds_off(row, 4 + fq));
-      fb[n] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    }
-    // one row of MFMA tiles at a time: only one A fragment is live
-#define MX_MFMA(m, n) acc[m][n] = mx_mfma<m, n>(fa, fb[n], acc[m][n], sca, scb)
-#define MX_MFMA_ROW(m)                                                            \
-  {                                                                               \
-    int row = wr * 64 + m * 16 + fr;                                              \
-    i32x4 lo = *reinterpret_cast<const i32x4*>(lds_a + mx_lds_off(row, fq));      \
-    i32x4 hi = *reinterpret_cast<const i32x4*>(lds_a + mx_lds_off(row, 4 + fq));  \
-    i32x8 fa = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);           \
-    MX_MFMA(m, 0); MX_MFMA(m, 1); MX_MFMA(m, 2); MX_MFMA(m, 3);                   \
+    for (int s = 0; s < kSubs; ++s) {
+      i32x8 fb[4];
+#pragma unroll
+      for (int n = 0; n < 4; ++n)
+        fb[n] = mx_frag<kSel>(lds_b, wc * 64 + n * 16 + fr, fq, s);
+      // one row of MFMA tiles at a time: only one A fragment is live
+#define MX_MFMA(m, n) \
+  acc[m][n] = mx_mfma<kSel, m, n>(fa, fb[n], acc[m][n], sca[s], scb[s])
+#define MX_MFMA_ROW(m)                                                   \
+  {                                                                      \
+    i32x8 fa = mx_frag<kSel>(lds_a, wr * 64 + m * 16 + fr, fq, s);       \
+    MX_MFMA(m, 0); MX_MFMA(m, 1); MX_MFMA(m, 2); MX_MFMA(m, 3);          \
   }
-    MX_MFMA_ROW(0);
-    MX_MFMA_ROW(1);
-    MX_MFMA_ROW(2);
-    MX_MFMA_ROW(3);
+      MX_MFMA_ROW(0);
+      MX_MFMA_ROW(1);
+      MX_MFMA_ROW(2);
+      MX_MFMA_ROW(3);
 #undef MX_MFMA_ROW
 #undef MX_MFMA
+    }
     __syncthreads();  // all fragment reads done before the next ds_write
   }
 
@@ -281,25 +326,56 @@ inline int mx_block_scale(const float* x, int n, int emax) {
   return static_cast<int>(std::min(254l, std::max(0l, e - emax + 127)));
 }
 
-}  // namespace detail
+// What tells the MX formats apart on the host. A format F has
+//   name          the payload's name in messages
+//   kBK           the kernel's K-step, in elements
+//   kPerByte      elements per byte of the device image
+//   kEmax         the exponent of the format's largest value
+//   kernel        the format's instantiation of gemm_mx_kernel
+//   encode        float -> element code, one per byte
+//   put           the code of element k into its byte of the image
+//   pack          a row of K codes, one per byte, into its image bytes
+struct Mxfp8 {
+  static constexpr const char* name = "mxgemm";
+  static constexpr int kBK = kMxBK;
+  static constexpr int kPerByte = 1;
+  static constexpr int kEmax = 8;  // 448 = 1.75 * 2^8
+  static constexpr auto kernel = gemm_mx_kernel<0>;
+  static uint8_t encode(float f) { return to_e4m3_sat(f); }
+  static void put(uint8_t& byte, size_t, uint8_t code) { byte = code; }
+  static void pack(const uint8_t* codes, int K, uint8_t* out) {
+    std::memcpy(out, codes, K);
+  }
+};
 
-// OCP MX quantization of one row of K floats: per block of 32 elements (a last
-// partial block as if padded with zeros) one E8M0 scale byte
-// clamp(floor(log2(amax)) - 8 + 127, 0, 254), 8 being the exponent of the
-// largest e4m3 (448 = 1.75 * 2^8), and the elements to_e4m3_sat(x / 2^(scale -
-// 127)). An all-zero block gets 127. codes: K bytes, scales: ceil(K / 32).
-// A NaN element becomes a NaN code and takes no part in amax.
-inline void mx_quantize_row(const float* x, int K, uint8_t* codes, uint8_t* scales) {
+// OCP MX quantization of one row of K floats to format F: per block of 32
+// elements (a last partial block as if padded with zeros) one E8M0 scale byte
+// clamp(floor(log2(amax)) - F::kEmax + 127, 0, 254) and the elements
+// F::encode(x * 2^(127 - scale)). An all-zero block gets 127. codes: K bytes,
+// one code each, scales: ceil(K / 32).
+template <class F>
+void mx_quantize_row(const float* x, int K, uint8_t* codes, uint8_t* scales) {
   for (int k0 = 0; k0 < K; k0 += kMxBlock) {
     const int n = std::min(kMxBlock, K - k0);
-    const int scale = detail::mx_block_scale(x + k0, n, 8);
+    const int scale = mx_block_scale(x + k0, n, F::kEmax);
     scales[k0 / kMxBlock] = static_cast<uint8_t>(scale);
-    // |127 - scale| <= 127 and x * 2^(127 - scale) < 2^9 whenever the clamp at
-    // 0 is not hit, so the scaling is exact unless the result is an fp32
-    // subnormal, which is far below half of 2^-9 and becomes zero either way
+    // |127 - scale| <= 127 and x * 2^(127 - scale) < 2^(kEmax + 1) whenever the
+    // clamp at 0 is not hit, so the power-of-two scaling is exact unless the
+    // result is an fp32 subnormal, which becomes zero either way. e4m3: < 2^9,
+    // and a subnormal is far below half of 2^-9. e2m1: < 8, and a subnormal is
+    // far below the first tie (0.25).
     for (int k = 0; k < n; ++k)
-      codes[k0 + k] = to_e4m3_sat(std::ldexp(x[k0 + k], 127 - scale));
+      codes[k0 + k] = F::encode(std::ldexp(x[k0 + k], 127 - scale));
   }
+}
+
+}  // namespace detail
+
+// OCP MX quantization of one row of K floats to e4m3 (detail::mx_quantize_row
+// with to_e4m3_sat). codes: K bytes, scales: ceil(K / 32). A NaN element
+// becomes a NaN code and takes no part in amax.
+inline void mx_quantize_row(const float* x, int K, uint8_t* codes, uint8_t* scales) {
+  detail::mx_quantize_row<detail::Mxfp8>(x, K, codes, scales);
 }
 
 // ---- host layer: the GEMM --------------------------------------------------
@@ -308,34 +384,11 @@ namespace detail {
 
 static_assert(kMxBM == kGemmBM && kMxBN == kGemmBN, "GemmShape pads M and N");
 
-// What tells the MX formats apart on the host. A format F has
-//   name          the payload's name in messages
-//   kBK           the kernel's K-step, in elements
-//   kPerByte      elements per byte of the device image
-//   kernel        the GEMM kernel (gemm_mxfp8_kernel's signature)
-//   encode        float -> element code, one per byte
-//   quantize_row  the format's mx*_quantize_row
-//   put           the code of element k into its byte of the image
-//   pack          a row of K codes, one per byte, into its image bytes
-struct Mxfp8 {
-  static constexpr const char* name = "mxgemm";
-  static constexpr int kBK = kMxBK;
-  static constexpr int kPerByte = 1;
-  static constexpr auto kernel = gemm_mxfp8_kernel;
-  static uint8_t encode(float f) { return to_e4m3_sat(f); }
-  static void quantize_row(const float* x, int K, uint8_t* codes, uint8_t* scales) {
-    mx_quantize_row(x, K, codes, scales);
-  }
-  static void put(uint8_t& byte, size_t, uint8_t code) { byte = code; }
-  static void pack(const uint8_t* codes, int K, uint8_t* out) {
-    std::memcpy(out, codes, K);
-  }
-};
-
 // Padded operands and scales of format F on the host plus their device images.
 template <class F>
 struct MxProblem : GemmShape {
-  size_t Kbytes, Kb;             // per padded row: operand bytes, scale bytes
+  static_assert(F::kBK == kMxBK * F::kPerByte, "a K-step row is 128 bytes");
+  size_t Kbytes, Kb;            // per padded row: operand bytes, scale bytes
   std::vector<uint8_t> a, bt;    // Mp x Kbytes, Np x Kbytes, zero-padded
   std::vector<uint8_t> sa, sbt;  // scale images (mx_scale_off), padded with 127
   DeviceBuffer da, dbt, dsa, dsbt;
@@ -468,14 +521,14 @@ void gemm_mx(const char* who, const float* a, const float* b, float* c, int M, i
   const size_t blocks = (static_cast<size_t>(K) + kMxBlock - 1) / kMxBlock;
   std::vector<uint8_t> codes(K), scales(blocks);
   for (int i = 0; i < M; ++i) {
-    F::quantize_row(a + static_cast<size_t>(i) * K, K, codes.data(), scales.data());
+    mx_quantize_row<F>(a + static_cast<size_t>(i) * K, K, codes.data(), scales.data());
     F::pack(codes.data(), K, p.row_a(i));
     scatter_scales(p.sa, i, p.Kb, scales.data(), blocks);
   }
   std::vector<float> col(K);
   for (int j = 0; j < N; ++j) {
     for (int k = 0; k < K; ++k) col[k] = b[static_cast<size_t>(k) * N + j];
-    F::quantize_row(col.data(), K, codes.data(), scales.data());
+    mx_quantize_row<F>(col.data(), K, codes.data(), scales.data());
     F::pack(codes.data(), K, p.row_bt(j));
     scatter_scales(p.sbt, j, p.Kb, scales.data(), blocks);
   }
