@@ -8,7 +8,7 @@ ROCM_ARCH ?= gfx950
 
 all: native
 
-native:  ## compile partitiond + payload + instaslice-stored, in-tree
+native:  ## compile partitiond + payload + instaslice-stored + _netwire, in-tree
 	PYTORCH_ROCM_ARCH=$(ROCM_ARCH) $(PYTHON) build_native.py
 
 test:    ## CPU test suite (no GPU needed)
@@ -46,5 +46,6 @@ undeploy:
 
 clean:
 	rm -f instaslice_amd/smi/_partitiond*.so instaslice_amd/ops/_payload*.so
+	rm -f instaslice_amd/store/_netwire*.so
 	rm -f instaslice_amd/bin/partitiond instaslice_amd/bin/instaslice-payload
 	find . -name __pycache__ -type d -exec rm -rf {} + 2>/dev/null || true

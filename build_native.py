@@ -8,6 +8,8 @@ but DO travel to the GPU box with the gpurun snapshot):
   instaslice_amd/bin/partitiond         standalone device daemon (stdio JSON)
   instaslice_amd/ops/_payload<EXT>      pybind11 module with gfx950 kernels
   instaslice_amd/bin/instaslice-payload standalone workload binary
+  instaslice_amd/bin/instaslice-stored  native store daemon (host C++)
+  instaslice_amd/store/_netwire<EXT>    pybind11 module: store client wire
 
 Usage: python build_native.py [--force]
 """
@@ -118,6 +120,16 @@ def build(force: bool = False) -> None:
     if force or not newer(out, [src, hdr2], "stored"):
         run(["g++", "-O2", "-std=c++17", "-pthread", src, "-o", out])
         record_hash(out, [src, hdr2], "stored")
+
+    # 6. _netwire pybind module: the store client's wire (framing, response
+    # demultiplexing, reader thread) off the GIL — host-only like stored
+    src = store_dir / "csrc" / "netwire_pybind.cpp"
+    hdr3 = store_dir / "csrc" / "netwire_core.hpp"
+    out = store_dir / f"_netwire{EXT}"
+    if force or not newer(out, [src, hdr3], "netwire"):
+        run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread",
+             "-fvisibility=hidden", *pybind_includes(), src, "-o", out])
+        record_hash(out, [src, hdr3], "netwire")
 
     print("native build complete")
 

@@ -20,8 +20,17 @@
 //     build replacements with copy-on-write along the touched path only —
 //     a patch clones ~hundreds of bytes of a ~3 KB CR, the rest is shared
 //   - watch notification under the lock is a pointer push into each
-//     matching connection's outbox; msgpack encoding happens in the
-//     per-connection writer threads, outside the lock, in parallel
+//     matching connection's outbox (which fixes event order per
+//     connection); once the lock is released the MUTATING thread itself
+//     encodes and sends what it queued, with a non-blocking send — no
+//     wake of another thread on the event's way out. One flusher drains a
+//     connection at a time; what the socket does not take at once (a slow
+//     consumer) is left to the connection's writer thread, which may block.
+//     Whole unsent frames go back to the front of the outbox; the rest of a
+//     frame sent in part does NOT — it is kept as `Conn::tail` under the
+//     socket's write mutex and goes out before anything else, because
+//     responses bypass the outbox (send_now) and would otherwise be
+//     written into the middle of that frame
 //   - reads (get/list) return shared references; responses are packed by
 //     the reader thread after the lock is released
 //
@@ -37,6 +46,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cerrno>
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -100,33 +110,51 @@ struct EventBlob {
   }
 };
 
-// per-connection outbox: responses and watch events share one ordered queue
-// flushed by a dedicated writer thread, so a slow consumer never blocks the
-// store mutex or another connection. Watch events enqueue as (watch_id,
-// shared EventBlob) and are packed by the writer thread.
+// per-connection outbox: one ordered queue, drained by one flusher at a time
+// (the mutating thread without blocking, else the connection's writer
+// thread), so a slow consumer never blocks the store mutex, a mutating
+// thread or another connection. Watch events enqueue as (watch_id, shared
+// EventBlob) and are packed by whoever flushes them.
 struct OutItem {
   std::string bytes;               // pre-framed (responses)
   int64_t wid = -1;                // >= 0: pack {watch_id, event} lazily
   std::shared_ptr<EventBlob> blob;
 };
 
-struct Conn {
-  int fd;
+std::string pack_event(const OutItem& it);  // below
+
+struct Conn : std::enable_shared_from_this<Conn> {
+  int fd = -1;
   std::mutex out_mu;
   std::condition_variable out_cv;
   std::deque<OutItem> outbox;
   bool closing = false;
+  // single-flusher protocol (under out_mu): whoever sets `flushing` owns
+  // the drain of `outbox` until it clears the flag again — the writer
+  // thread or a mutating thread (flush_inline), never two at once, so the
+  // outbox's FIFO order is the wire's order
+  bool flushing = false;
   std::vector<std::shared_ptr<WatchSub>> subs;
-  // serializes actual socket writes between the writer thread and the
-  // reader's inline response path (send_now) — byte interleave guard
+  // serializes actual socket writes between the flusher and the reader's
+  // inline response path (send_now) — byte interleave guard
   std::mutex write_mu;
+  // under write_mu: the rest of a frame that a non-blocking flush could
+  // only send in part. Whoever writes next sends it first, so no other
+  // bytes can land inside that frame.
+  std::string tail;
+  std::atomic<bool> tail_pending{false};
 
-  bool raw_send(const std::string& data) {
-    std::lock_guard<std::mutex> g(write_mu);
-    const char* p = data.data();
-    size_t left = data.size();
+  // the fd lives as long as any thread may still write to it (mutating
+  // threads hold a reference while they flush), so its number cannot be
+  // handed to a new connection under them
+  ~Conn() {
+    if (fd >= 0) ::close(fd);
+  }
+
+  static bool send_all(int fd, const char* p, size_t left) {
     while (left > 0) {
       ssize_t n = ::send(fd, p, left, MSG_NOSIGNAL);
+      if (n < 0 && errno == EINTR) continue;
       if (n <= 0) return false;
       p += n;
       left -= static_cast<size_t>(n);
@@ -134,11 +162,86 @@ struct Conn {
     return true;
   }
 
-  // responses skip the outbox + writer wakeup when nothing is queued —
+  bool raw_send(const std::string& data) {
+    std::lock_guard<std::mutex> g(write_mu);
+    if (!tail.empty()) {
+      if (!send_all(fd, tail.data(), tail.size())) return false;
+      tail.clear();
+      tail_pending.store(false);
+    }
+    return send_all(fd, data.data(), data.size());
+  }
+
+  // Drain the outbox from the thread that just filled it, without ever
+  // waiting for the peer: what a non-blocking send does not take is left
+  // to the writer thread. Saves the futex wake + context switch to the
+  // writer on every watch-event hop of a lifecycle.
+  void flush_inline() {
+    std::deque<OutItem> batch;
+    {
+      std::lock_guard<std::mutex> g(out_mu);
+      if (flushing || closing || outbox.empty()) return;
+      if (tail_pending.load()) {  // socket is full: the writer's business
+        out_cv.notify_one();
+        return;
+      }
+      flushing = true;
+      batch.swap(outbox);
+    }
+    std::string data;
+    for (auto& it : batch)
+      data += (it.wid >= 0) ? pack_event(it) : std::move(it.bytes);
+    bool failed = false;
+    bool requeue = false;  // whole frames back to the outbox's front
+    {
+      std::unique_lock<std::mutex> w(write_mu, std::try_to_lock);
+      if (!w.owns_lock()) {
+        // a blocking sender (a response to a slow peer) is on the socket
+        requeue = true;
+      } else {
+        // older bytes first; on the usual path there are none and `data`
+        // goes out as it stands
+        const bool had_tail = !tail.empty();
+        if (had_tail) tail += data;
+        const std::string& src = had_tail ? tail : data;
+        size_t off = 0;
+        while (off < src.size()) {
+          ssize_t n = ::send(fd, src.data() + off, src.size() - off,
+                             MSG_NOSIGNAL | MSG_DONTWAIT);
+          if (n < 0 && errno == EINTR) continue;
+          if (n < 0 && (errno == EAGAIN || errno == EWOULDBLOCK)) break;
+          if (n <= 0) { failed = true; break; }
+          off += static_cast<size_t>(n);
+        }
+        if (had_tail) tail.erase(0, off);
+        else if (off < data.size()) tail.assign(data, off, std::string::npos);
+        tail_pending.store(!tail.empty());
+      }
+    }
+    std::lock_guard<std::mutex> g(out_mu);
+    flushing = false;
+    if (failed) {
+      closing = true;
+      outbox.clear();
+      ::shutdown(fd, SHUT_RDWR);
+      out_cv.notify_one();
+      return;
+    }
+    if (requeue && !closing) {
+      OutItem it;
+      it.bytes = std::move(data);
+      outbox.push_front(std::move(it));
+    }
+    if (!outbox.empty() || tail_pending.load()) out_cv.notify_one();
+  }
+
+  // responses always skip the outbox + writer wakeup, whatever is queued —
   // one fewer thread handoff on every request's critical path. A response
   // may overtake QUEUED watch events; the protocol tolerates that
   // (responses and events resolve independently client-side; only
-  // event-vs-event order matters, and that stays in the outbox).
+  // event-vs-event order matters, and that stays in the outbox). What a
+  // response must never do is land INSIDE a half-sent event frame: hence
+  // `tail`, which raw_send finishes first.
   void send_now(const std::string& frame_bytes) {
     {
       std::lock_guard<std::mutex> g(out_mu);
@@ -228,6 +331,8 @@ inline void cow_map(Value& v) {
 
 using ObjPtr = std::shared_ptr<const Value>;
 
+using WakeList = std::vector<std::shared_ptr<Conn>>;
+
 class Store {
  public:
   // key = kind \x00 ns \x00 name (lexicographic == Python tuple sort)
@@ -255,7 +360,7 @@ class Store {
   // `obj` is moved in: the reader thread owns the freshly unpacked request,
   // so no defensive copy is needed before mutation
   Value create(Value&& obj) {
-    std::vector<Conn*> wake;
+    WakeList wake;
     Value out;
     {
       std::lock_guard<std::mutex> g(mu_);
@@ -268,7 +373,7 @@ class Store {
       notify_locked("ADDED", stored, wake);
       out = *stored;
     }
-    for (Conn* c : wake) c->out_cv.notify_one();
+    for (auto& c : wake) c->flush_inline();
     mark_dirty();
     return out;
   }
@@ -299,7 +404,7 @@ class Store {
   }
 
   Value update(Value&& obj) {
-    std::vector<Conn*> wake;
+    WakeList wake;
     Value out;
     {
     std::lock_guard<std::mutex> g(mu_);
@@ -325,13 +430,13 @@ class Store {
     }
     out = commit_locked(k, std::move(obj), wake);
     }
-    for (Conn* c : wake) c->out_cv.notify_one();
+    for (auto& c : wake) c->flush_inline();
     mark_dirty();
     return out;
   }
 
   void del(const std::string& kind, const std::string& ns, const std::string& name) {
-    std::vector<Conn*> wake;
+    WakeList wake;
     {
     std::lock_guard<std::mutex> g(mu_);
     std::string k = key(kind, ns, name);
@@ -367,13 +472,13 @@ class Store {
       notify_locked("DELETED", gone, wake);
     }
     }
-    for (Conn* c : wake) c->out_cv.notify_one();
+    for (auto& c : wake) c->flush_inline();
     mark_dirty();
   }
 
   Value patch(const std::string& kind, const std::string& ns,
               const std::string& name, const Value& ops) {
-    std::vector<Conn*> wake;
+    WakeList wake;
     Value out;
     {
       std::lock_guard<std::mutex> g(mu_);
@@ -389,7 +494,7 @@ class Store {
       bump_rv(obj);
       out = commit_locked(k, std::move(obj), wake);
     }
-    for (Conn* c : wake) c->out_cv.notify_one();
+    for (auto& c : wake) c->flush_inline();
     mark_dirty();
     return out;
   }
@@ -437,7 +542,7 @@ class Store {
       }
       watches_.push_back(std::move(sub));
     }
-    if (pushed) conn->out_cv.notify_one();
+    if (pushed) conn->flush_inline();
   }
 
   void drop_conn_watches(Conn* c) {
@@ -463,7 +568,7 @@ class Store {
   // shared commit tail for update/patch: store, handle finalizer-free
   // deletion, notify
   Value commit_locked(const std::string& k, Value obj,
-                      std::vector<Conn*>& wake) {
+                      WakeList& wake) {
     ObjPtr stored = std::make_shared<const Value>(std::move(obj));
     const Value* md = stored->find("metadata");
     const Value* dt = md ? md->find("deletionTimestamp") : nullptr;
@@ -627,7 +732,7 @@ class Store {
   // under the lock: pointer pushes only — packing happens in writer threads
   // and the futex wakes are deferred to after the store mutex is released
   void notify_locked(const char* type, const ObjPtr& obj,
-                     std::vector<Conn*>& wake) {
+                     WakeList& wake) {
     // bounded event history for watch resume (rv_ was bumped by the
     // mutation that triggers this notify, so it is the event's revision)
     history_.emplace_back(rv_, std::string(type), obj);
@@ -640,7 +745,12 @@ class Store {
       if (!matches(*w, *obj)) continue;
       if (!blob) blob = std::make_shared<EventBlob>(type, obj);
       w->conn->enqueue_event_silent(w->watch_id, blob);
-      if (wake.empty() || wake.back() != w->conn) wake.push_back(w->conn);
+      // a reference, not a pointer: the flush runs after the store mutex
+      // is released, when the connection's own threads may be tearing down
+      // (under mu_ a live subscription's Conn is still alive: its reader
+      // only lets go after drop_conn_watches, which takes mu_)
+      if (wake.empty() || wake.back().get() != w->conn)
+        wake.push_back(w->conn->shared_from_this());
     }
     if (any_dead) {
       watches_.erase(std::remove_if(watches_.begin(), watches_.end(),
@@ -794,15 +904,26 @@ void writer_loop(std::shared_ptr<Conn> conn) {
     std::deque<OutItem> batch;
     {
       std::unique_lock<std::mutex> g(conn->out_mu);
-      conn->out_cv.wait(g, [&] { return conn->closing || !conn->outbox.empty(); });
-      if (conn->closing && conn->outbox.empty()) return;
+      // same single-flusher protocol as Conn::flush_inline, but this
+      // thread may block on the socket: it takes what the mutating threads
+      // could not send without waiting (and everything that queues up
+      // behind it while it is blocked)
+      conn->out_cv.wait(g, [&] {
+        return conn->closing ||
+               (!conn->flushing &&
+                (!conn->outbox.empty() || conn->tail_pending.load()));
+      });
+      if (conn->closing) return;
+      conn->flushing = true;
       batch.swap(conn->outbox);
     }
     std::string data;
     for (auto& it : batch)
       data += (it.wid >= 0) ? pack_event(it) : std::move(it.bytes);
-    if (!conn->raw_send(data)) {
-      std::lock_guard<std::mutex> g(conn->out_mu);
+    bool ok = conn->raw_send(data);
+    std::lock_guard<std::mutex> g(conn->out_mu);
+    conn->flushing = false;
+    if (!ok) {
       conn->closing = true;
       conn->outbox.clear();
       return;
@@ -928,7 +1049,9 @@ void reader_loop(Store& store, std::shared_ptr<Conn> conn) {
   }
   conn->out_cv.notify_one();
   writer.join();
-  ::close(conn->fd);
+  // the peer sees the end now; the fd itself is closed with the last
+  // reference to the Conn (a mutating thread may still be flushing to it)
+  ::shutdown(conn->fd, SHUT_RDWR);
 }
 
 }  // namespace stored

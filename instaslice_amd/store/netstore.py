@@ -25,11 +25,14 @@ update_with_retry) behave identically to the in-memory store.
 
 from __future__ import annotations
 
+import atexit
+import os
 import queue
 import socket
 import socketserver
 import struct
 import threading
+import weakref
 from typing import Callable, List, Optional, Tuple
 
 import msgpack
@@ -41,6 +44,11 @@ from instaslice_amd.store.memstore import (
     NotFound,
 )
 from instaslice_amd.utils import get_logger
+
+try:  # built by build_native.py; without it the pure-Python wire below runs
+    from instaslice_amd.store import _netwire
+except ImportError:
+    _netwire = None
 
 _EXC_BY_NAME = {
     "Conflict": Conflict,
@@ -245,7 +253,10 @@ class _ClientWatch:
 
                     traceback.print_exc()
                 return
-        self._q.put(event)
+            # under the lock: a set_callback draining the queue right now
+            # must either see this event or have installed its callback
+            # before we looked — queued behind the drain it would be lost
+            self._q.put(event)
 
     def next(self, timeout: Optional[float] = None) -> Optional[Tuple[str, dict]]:
         try:
@@ -258,8 +269,37 @@ class _ClientWatch:
         self._q.put(None)
 
 
+def _native_wire_enabled() -> bool:
+    return (_netwire is not None
+            and os.environ.get("INSTASLICE_NATIVE_WIRE", "1") != "0")
+
+
+# clients whose native reader thread is alive: closed at interpreter exit,
+# before finalization — a native thread that wants the GIL for a callback
+# while the interpreter is going down would be stuck or killed mid-frame
+_live_wires: "weakref.WeakSet" = weakref.WeakSet()
+
+
+@atexit.register
+def _close_live_wires() -> None:
+    for c in list(_live_wires):
+        try:
+            c.close()
+        except Exception:  # noqa: BLE001 - best effort at exit
+            pass
+
+
 class NetStoreClient:
     """Store client with the MemStore interface (duck-typed).
+
+    Without reconnect, and when the _netwire extension is built (and
+    INSTASLICE_NATIVE_WIRE is not "0"), the wire is native: a C++ reader
+    thread cuts frames off the socket without the GIL and hands each
+    response's bytes directly to the thread blocked in _call, which decodes
+    them itself; only watch events come back into Python on the reader
+    (store/csrc/netwire_core.hpp). The pure-Python reader below stays for
+    reconnect=True (it reads its own resubscribe responses inline) and as the
+    fallback; both present identical semantics.
 
     With reconnect=True (long-running daemons), a lost connection is
     re-established with exponential backoff and every live watch is
@@ -277,7 +317,6 @@ class NetStoreClient:
         self._sock = socket.create_connection((host, port), timeout=timeout)
         self._sock.settimeout(None)
         self._sock.setsockopt(socket.IPPROTO_TCP, socket.TCP_NODELAY, 1)
-        self._rfile = self._sock.makefile("rb")
         self._wlock = threading.Lock()
         self._pending: dict = {}
         self._watches: dict = {}
@@ -292,9 +331,43 @@ class NetStoreClient:
         self._idlock = threading.Lock()
         self._closed = False
         self.log = get_logger("netstore.client")
-        self._reader = threading.Thread(target=self._read_loop,
-                                        name="netstore-reader", daemon=True)
-        self._reader.start()
+        self._wire = None
+        self._reader = None
+        if not reconnect and _native_wire_enabled():
+            # the wire BORROWS the fd: self._sock stays the owner and is
+            # closed only after the wire's reader is joined (see close()).
+            # Weak callbacks: the extension object is invisible to the cycle
+            # collector, a bound method would pin this client forever.
+            ref = weakref.ref(self)
+
+            def on_frame(payload: bytes) -> None:
+                me = ref()
+                if me is not None:
+                    me._dispatch(msgpack.unpackb(payload, raw=False))
+
+            def on_closed() -> None:
+                me = ref()
+                if me is not None:
+                    me._wire_closed()
+
+            self._wire = _netwire.Wire(self._sock.fileno(), on_frame,
+                                       on_closed, self._sock)
+            _live_wires.add(self)
+        else:
+            self._rfile = self._sock.makefile("rb")
+            self._reader = threading.Thread(target=self._read_loop,
+                                            name="netstore-reader",
+                                            daemon=True)
+            self._reader.start()
+
+    def _wire_closed(self) -> None:
+        """The native reader is gone (EOF, error or close()): the tail of
+        _read_loop. Pending calls were already failed natively."""
+        self._closed = True
+        with self._watch_reg_lock:
+            watches = list(self._watches.values())
+        for w in watches:
+            w.stop()
 
     def _dispatch(self, msg: dict) -> None:
         if "watch_id" in msg and "event" in msg:
@@ -420,9 +493,27 @@ class NetStoreClient:
         with self._idlock:
             self._next_id += 1
             rid = self._next_id
+        req = _pack({"id": rid, "verb": verb, **kw})
+        if self._wire is not None:
+            # send + wait natively, GIL released; the response comes back as
+            # bytes and is decoded HERE, on the thread that wants it
+            try:
+                payload = self._wire.call(rid, req, 60.0)
+            except TimeoutError:
+                raise TimeoutError(f"netstore call {verb} timed out") from None
+            msg = msgpack.unpackb(payload, raw=False)
+        else:
+            msg = self._call_py(rid, verb, req)
+        if msg["ok"]:
+            return msg.get("result")
+        err = msg["error"]
+        if err["type"] == "Error" and "connection" in err["msg"]:
+            raise ConnectionError(err["msg"])
+        raise _EXC_BY_NAME.get(err["type"], RuntimeError)(err["msg"])
+
+    def _call_py(self, rid: int, verb: str, req: bytes) -> dict:
         ev = [threading.Event(), None]
         self._pending[rid] = ev
-        req = _pack({"id": rid, "verb": verb, **kw})
         try:
             with self._wlock:
                 self._sock.sendall(req)
@@ -432,13 +523,7 @@ class NetStoreClient:
         if not ev[0].wait(timeout=60.0):
             self._pending.pop(rid, None)
             raise TimeoutError(f"netstore call {verb} timed out")
-        msg = ev[1]
-        if msg["ok"]:
-            return msg.get("result")
-        err = msg["error"]
-        if err["type"] == "Error" and "connection" in err["msg"]:
-            raise ConnectionError(err["msg"])
-        raise _EXC_BY_NAME.get(err["type"], RuntimeError)(err["msg"])
+        return ev[1]
 
     # -- MemStore interface -------------------------------------------------
 
@@ -510,6 +595,11 @@ class NetStoreClient:
 
     def close(self) -> None:
         self._closed = True
+        if self._wire is not None:
+            # shuts the socket down, fails pending calls, joins the reader:
+            # nothing touches the fd or calls back once this returns
+            self._wire.close()
+            self._wire_closed()
         try:
             self._sock.close()
         except OSError:
