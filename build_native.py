@@ -115,21 +115,23 @@ def build(force: bool = False) -> None:
     # no ROCm dependency; runs on any node incl. the CPU test tier)
     store_dir = ROOT / "instaslice_amd" / "store"
     src = store_dir / "csrc" / "stored_main.cpp"
-    hdr2 = store_dir / "csrc" / "msgpack_value.hpp"
+    stored_hdrs = [store_dir / "csrc" / h for h in
+                   ("stored_core.hpp", "msgpack_value.hpp", "wire_frame.hpp")]
     out = bin_dir / "instaslice-stored"
-    if force or not newer(out, [src, hdr2], "stored"):
+    if force or not newer(out, [src, *stored_hdrs], "stored"):
         run(["g++", "-O2", "-std=c++17", "-pthread", src, "-o", out])
-        record_hash(out, [src, hdr2], "stored")
+        record_hash(out, [src, *stored_hdrs], "stored")
 
     # 6. _netwire pybind module: the store client's wire (framing, response
     # demultiplexing, reader thread) off the GIL — host-only like stored
     src = store_dir / "csrc" / "netwire_pybind.cpp"
-    hdr3 = store_dir / "csrc" / "netwire_core.hpp"
+    netwire_hdrs = [store_dir / "csrc" / h for h in
+                    ("netwire_core.hpp", "wire_frame.hpp")]
     out = store_dir / f"_netwire{EXT}"
-    if force or not newer(out, [src, hdr3], "netwire"):
+    if force or not newer(out, [src, *netwire_hdrs], "netwire"):
         run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread",
              "-fvisibility=hidden", *pybind_includes(), src, "-o", out])
-        record_hash(out, [src, hdr3], "netwire")
+        record_hash(out, [src, *netwire_hdrs], "netwire")
 
     print("native build complete")
 

@@ -36,6 +36,8 @@
 #include <unordered_map>
 #include <vector>
 
+#include "wire_frame.hpp"
+
 #if defined(__SANITIZE_THREAD__)  // gcc
 #define NETWIRE_TSAN 1
 #elif defined(__has_feature)
@@ -45,8 +47,6 @@
 #endif
 
 namespace netwire {
-
-constexpr uint32_t kMaxFrame = 64u << 20;  // as the daemon: larger closes
 
 // ---- msgpack: walk the top-level map's keys, skip everything else ---------
 
@@ -411,12 +411,8 @@ class Wire : public std::enable_shared_from_this<Wire> {
       // cut every complete frame out of [rpos, wpos)
       bool bad = false;
       while (wpos - rpos >= 4) {
-        const unsigned char* h =
-            reinterpret_cast<const unsigned char*>(buf.data() + rpos);
-        uint32_t len = (static_cast<uint32_t>(h[0]) << 24) |
-                       (static_cast<uint32_t>(h[1]) << 16) |
-                       (static_cast<uint32_t>(h[2]) << 8) | h[3];
-        if (len > kMaxFrame) { bad = true; break; }
+        uint32_t len = wire::frame_len(buf.data() + rpos);
+        if (len > wire::kMaxFrame) { bad = true; break; }
         if (wpos - rpos - 4 < len) {
           size_t need = static_cast<size_t>(len) + 4;
           if (buf.size() - rpos < need) {

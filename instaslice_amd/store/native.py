@@ -1,6 +1,6 @@
 """Native store daemon wrapper: spawn/stop `instaslice-stored`.
 
-The daemon (store/csrc/stored_main.cpp) speaks the exact netstore protocol,
+The daemon (store/csrc/stored_core.hpp) speaks the exact netstore protocol,
 so NetStoreClient works against it unchanged. Used by the control plane when
 wire throughput matters (many agents / sharded controllers) and by the CPU
 test tier for protocol-parity checks against MemStore."""

@@ -1,6 +1,6 @@
 // Stand-alone self-test of store/csrc/netwire_core.hpp over a socketpair.
 // No Python, no GPU: build with -fsanitize=address,undefined and with
-// -fsanitize=thread and run directly (tests/test_netwire_selftest.py does).
+// -fsanitize=thread and run directly (tests/test_native_selftests.py does).
 //
 // The test plays the server on one end of the pair; a Wire owns the other.
 

@@ -1,7 +1,7 @@
 """Protocol-parity battery: the C++ store daemon (instaslice-stored) must be
 indistinguishable from MemStore behind NetStoreClient. Every scenario runs
 against BOTH backends via the parametrized fixture; the native daemon is the
-control plane's scale-out path (store/csrc/stored_main.cpp), MemStore the
+control plane's scale-out path (store/csrc/stored_core.hpp), MemStore the
 reference semantics (store/memstore.py)."""
 
 import os

@@ -1,5 +1,5 @@
 """instaslice-stored sends a watch event from the thread that made the
-mutation (store/csrc/stored_main.cpp, Conn::flush_inline). What must not
+mutation (store/csrc/stored_core.hpp, Conn::flush_inline). What must not
 change with that: event order per connection, writers never waiting for a
 slow watcher, the outbox cap, and the subscribe response coming first."""
 
