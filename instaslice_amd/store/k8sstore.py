@@ -18,12 +18,19 @@ Mapping:
 
 from __future__ import annotations
 
-import queue
 import threading
-from typing import Callable, List, Optional
+from typing import List, Optional
 
 from instaslice_amd import API_GROUP, API_VERSION
-from instaslice_amd.store.memstore import AlreadyExists, Conflict, NotFound
+from instaslice_amd.store.memstore import (
+    AlreadyExists,
+    Conflict,
+    NotFound,
+    StoreVerbs,
+    WatchQueue,
+    _filter_matches,
+    apply_patch_ops,
+)
 from instaslice_amd.utils import get_logger
 
 
@@ -39,24 +46,7 @@ def _require_k8s():
         ) from e
 
 
-class _K8sWatch:
-    def __init__(self) -> None:
-        self._q: "queue.Queue[Optional[Tuple[str, dict]]]" = queue.Queue()
-        self._stopped = False
-        self.kind: Optional[str] = None
-
-    def next(self, timeout: Optional[float] = None):
-        try:
-            return self._q.get(timeout=timeout)
-        except queue.Empty:
-            return None
-
-    def stop(self) -> None:
-        self._stopped = True
-        self._q.put(None)
-
-
-class K8sStore:
+class K8sStore(StoreVerbs):
     """MemStore-compatible adapter over a live API server."""
 
     def __init__(self, namespace_default: str = "default") -> None:
@@ -85,9 +75,6 @@ class K8sStore:
                 raise AlreadyExists(f"{kind}/{name} exists") from None
             raise Conflict(f"{kind}/{name}: {msg}") from None
         raise
-
-    def _route(self, kind: str):
-        return kind  # dispatch happens in each verb
 
     @staticmethod
     def _to_dict(obj) -> dict:
@@ -282,13 +269,10 @@ class K8sStore:
             # one upstream watch per distinct kind named in the filters,
             # client-side filtered (k8s field selectors could narrow further;
             # correctness first)
-            from instaslice_amd.store.memstore import _filter_matches
-
             kinds = {f.get("kind") for f in filters}
             if None in kinds:
                 raise ValueError("K8sStore filters need explicit kinds")
-            merged = _K8sWatch()
-            merged.kind = None
+            merged = WatchQueue()
             for knd in sorted(kinds):
                 inner = self.watch(knd, replay=replay)
 
@@ -298,7 +282,7 @@ class K8sStore:
                         if ev is None:
                             continue
                         if any(_filter_matches(f, ev[1]) for f in filters):
-                            merged._q.put(ev)
+                            merged._deliver(ev)
                     inner.stop()
 
                 t = threading.Thread(target=forward, daemon=True,
@@ -306,8 +290,7 @@ class K8sStore:
                 t.start()
                 self._watch_threads.append(t)
             return merged
-        w = _K8sWatch()
-        w.kind = kind
+        w = WatchQueue(kind)
 
         def pump():
             # LIST+WATCH, the controller-runtime informer protocol: the
@@ -328,7 +311,7 @@ class K8sStore:
                                 return
                             rv = max(rv, int(
                                 o["metadata"].get("resourceVersion", "0")))
-                            w._q.put(("ADDED", o))
+                            w._deliver(("ADDED", o))
                     kwargs = {"timeout_seconds": 30}
                     if rv is not None:
                         kwargs["resource_version"] = str(rv)
@@ -351,7 +334,7 @@ class K8sStore:
                                 rv = max(rv or 0, int(new_rv))
                             except ValueError:
                                 pass
-                        w._q.put((ev["type"], obj))
+                        w._deliver((ev["type"], obj))
                 except Exception as e:  # reconnect loop (API server restarts)
                     if w._stopped:
                         return
@@ -372,7 +355,6 @@ class K8sStore:
         """PATCH emulation over get+update (real k8s rejects unknown-verb
         shortcuts; server-side-apply would be the native path). Failed test
         ops raise Conflict straight through — same contract as MemStore."""
-        from instaslice_amd.store.memstore import apply_patch_ops
 
         def mut(obj: dict):
             apply_patch_ops(obj, ops or [])
@@ -382,51 +364,3 @@ class K8sStore:
         if res is None:
             raise NotFound(f"{kind}/{name} not found")
         return res
-
-    def batch(self, requests: list, *, quiet: bool = False) -> list:
-        out = []
-        for req in requests:
-            verb = req.get("verb")
-            try:
-                if verb == "create":
-                    res = self.create(req["obj"])
-                elif verb == "get":
-                    res = self.get(req["kind"], req["name"], req.get("namespace", ""))
-                elif verb == "update":
-                    res = self.update(req["obj"])
-                elif verb == "delete":
-                    self.delete(req["kind"], req["name"], req.get("namespace", ""))
-                    res = None
-                elif verb == "patch":
-                    res = self.patch(req["kind"], req["name"],
-                                     req.get("namespace", ""), req.get("ops"))
-                else:
-                    raise ValueError(f"unknown batch verb {verb!r}")
-                out.append({"ok": True, "result": res})
-            except (Conflict, NotFound, AlreadyExists) as e:
-                out.append({"ok": False,
-                            "error": {"type": type(e).__name__, "msg": str(e)}})
-        return out
-
-    def update_with_retry(
-        self, kind: str, name: str, namespace: str,
-        mutate: Callable[[dict], Optional[dict]], attempts: int = 25,
-    ):
-        for attempt in range(attempts):
-            try:
-                obj = self.get(kind, name, namespace)
-            except NotFound:
-                return None
-            new = mutate(obj)
-            if new is None:
-                return None
-            try:
-                return self.update(new)
-            except Conflict:
-                if attempt >= 2:  # hot object: jittered backoff breaks livelock
-                    import random
-                    import time as _time
-
-                    _time.sleep(random.random() * 0.002 * attempt)
-                continue
-        raise Conflict(f"update_with_retry exhausted for {kind}/{name}")

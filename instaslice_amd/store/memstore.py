@@ -22,8 +22,14 @@ store used by multi-rank benchmarks (store/netstore.py).
 from __future__ import annotations
 
 import json
+import os
 import queue
+import random
+import tempfile
 import threading
+import time
+import traceback
+from collections import deque
 from typing import Callable, Dict, List, Optional, Tuple
 
 
@@ -180,31 +186,19 @@ def _filter_matches(f: dict, obj: dict) -> bool:
     return True
 
 
-class Watch:
-    """A subscription delivering (event_type, object) tuples.
+class WatchQueue:
+    """The event queue behind every store's watch: (event_type, object)
+    tuples, read with `next` or pushed into a callback.
 
-    event_type is "ADDED" | "MODIFIED" | "DELETED". Objects are deep copies.
-    `filters` (list of {kind,name,namespace,labels} dicts, OR-combined) scope
-    the subscription server-side — the k8s field/label-selector analog. A
-    cluster-wide all-kinds watch is O(total event rate); filtered watches keep
-    per-client traffic O(own events), which is what lets N node agents share
-    one store without N^2 event fan-out.
-    """
+    event_type is "ADDED" | "MODIFIED" | "DELETED". Event objects are shared
+    and read-only by contract."""
 
-    def __init__(self, store: "MemStore", kind: Optional[str],
-                 filters: Optional[List[dict]] = None):
-        self._store = store
+    def __init__(self, kind: Optional[str] = None) -> None:
         self.kind = kind
-        self.filters = filters
         self._q: "queue.Queue[Optional[Tuple[str, dict]]]" = queue.Queue()
         self._stopped = False
         self._cb = None
         self._cb_lock = threading.Lock()
-
-    def _matches(self, obj: dict) -> bool:
-        if self.filters is not None:
-            return any(_filter_matches(f, obj) for f in self.filters)
-        return self.kind is None or self.kind == obj["kind"]
 
     def set_callback(self, fn) -> None:
         """Push-mode delivery: events invoke `fn(event_type, obj)` directly
@@ -224,19 +218,20 @@ class Watch:
                     fn(*ev)
             self._cb = fn
 
-    def _push(self, event: Tuple[str, dict]) -> None:
-        if self._stopped:
-            return
+    def _deliver(self, event: Tuple[str, dict]) -> None:
         with self._cb_lock:
+            if self._stopped:
+                return
             if self._cb is not None:
                 try:
                     self._cb(*event)
-                except Exception:  # noqa: BLE001 - consumer bug must not kill notify
-                    import traceback
-
+                except Exception:  # noqa: BLE001 - consumer bug must not kill the notifier
                     traceback.print_exc()
                 return
-        self._q.put(event)
+            # under the lock: a set_callback draining the queue right now
+            # must either see this event or have installed its callback
+            # before we looked — queued behind the drain it would be lost
+            self._q.put(event)
 
     def next(self, timeout: Optional[float] = None) -> Optional[Tuple[str, dict]]:
         """Blocking next event; None on stop or timeout."""
@@ -250,12 +245,108 @@ class Watch:
         self._q.put(None)
 
 
-class MemStore:
+class Watch(WatchQueue):
+    """A MemStore subscription. Objects are deep copies.
+
+    `filters` (list of {kind,name,namespace,labels} dicts, OR-combined) scope
+    the subscription server-side — the k8s field/label-selector analog. A
+    cluster-wide all-kinds watch is O(total event rate); filtered watches keep
+    per-client traffic O(own events), which is what lets N node agents share
+    one store without N^2 event fan-out.
+    """
+
+    def __init__(self, kind: Optional[str],
+                 filters: Optional[List[dict]] = None) -> None:
+        super().__init__(kind)
+        self.filters = filters
+
+    def _matches(self, obj: dict) -> bool:
+        if self.filters is not None:
+            return any(_filter_matches(f, obj) for f in self.filters)
+        return self.kind is None or self.kind == obj["kind"]
+
+
+def execute(store, req: dict):
+    """Dispatch one request dict onto a store: the single-verb path of the
+    TCP server and every entry of a batch (`execute` in stored_core.hpp is
+    the daemon's copy)."""
+    verb = req.get("verb")
+    if verb == "create":
+        return store.create(req["obj"])
+    if verb == "get":
+        return store.get(req["kind"], req["name"], req.get("namespace", ""))
+    if verb == "list":
+        return store.list(req["kind"], req.get("namespace"))
+    if verb == "update":
+        return store.update(req["obj"])
+    if verb == "delete":
+        store.delete(req["kind"], req["name"], req.get("namespace", ""))
+        return None
+    if verb == "patch":
+        return store.patch(req["kind"], req["name"], req.get("namespace", ""),
+                           req.get("ops"))
+    if verb == "ping":
+        return "pong"
+    raise ValueError(f"unknown verb {verb!r}")
+
+
+class StoreVerbs:
+    """What every store builds from its own create/get/list/update/delete/
+    patch: the batch loop and the conflict-retry loop."""
+
+    retry_attempts = 25
+
+    def batch(self, requests: List[dict], *, quiet: bool = False) -> List[dict]:
+        """Execute several verbs in one call; per-entry results so callers
+        keep the same error semantics as individual calls. Over the TCP store
+        this collapses the agent's serial create-path writes (ConfigMap +
+        Node capacity + CR commit) into a single round-trip. With `quiet`,
+        per-entry ok/error survives and the result payloads are dropped."""
+        out: List[dict] = []
+        for req in requests:
+            try:
+                res = execute(self, req)
+                out.append({"ok": True, "result": None if quiet else res})
+            except (Conflict, NotFound, AlreadyExists) as e:
+                out.append({"ok": False, "result": None,
+                            "error": {"type": type(e).__name__, "msg": str(e)}})
+        return out
+
+    def update_with_retry(
+        self, kind: str, name: str, namespace: str,
+        mutate: Callable[[dict], Optional[dict]],
+        attempts: Optional[int] = None,
+    ) -> Optional[dict]:
+        """Get-mutate-update loop absorbing Conflicts. `mutate` returns the
+        modified object or None to abort. This is the pattern the reference
+        implements as requeue-on-conflict (instaslice_controller.go:93)."""
+        if attempts is None:
+            attempts = self.retry_attempts
+        for attempt in range(attempts):
+            try:
+                obj = self.get(kind, name, namespace)
+            except NotFound:
+                return None
+            new = mutate(obj)
+            if new is None:
+                return None
+            try:
+                return self.update(new)
+            except Conflict:
+                if attempt >= 2:  # hot object: jittered backoff breaks livelock
+                    time.sleep(random.random() * 0.002 * attempt)
+                continue
+        raise Conflict(f"update_with_retry: {attempts} attempts exhausted for {kind}/{name}")
+
+
+class MemStore(StoreVerbs):
     """Thread-safe object store with k8s-like verbs.
 
     All returned objects are deep copies: mutating them does not change the
     store (matching client-go cache semantics the reference relies on).
     """
+
+    retry_attempts = 10
 
     def __init__(self, persist_path: Optional[str] = None,
                  persist_debounce_s: float = 0.2) -> None:
@@ -264,8 +355,6 @@ class MemStore:
         self._rv = 0
         self._watches: List[Watch] = []
         # bounded event history: (event_rv, type, obj) — watch resume tokens
-        from collections import deque
-
         self._history: "deque" = deque(maxlen=8192)
         # Durability (checkpoint/resume): the reference keeps all state in
         # etcd; for standalone deployments this store can
@@ -286,8 +375,6 @@ class MemStore:
     # -- persistence --------------------------------------------------------
 
     def _load(self) -> None:
-        import os
-
         if not self._persist_path or not os.path.exists(self._persist_path):
             return
         with open(self._persist_path) as f:
@@ -297,44 +384,41 @@ class MemStore:
             for obj in snap.get("objects", []):
                 self._objects[_key(obj)] = obj
 
-    def _persist_loop(self) -> None:
-        import os
-        import tempfile
+    def _write_snapshot(self) -> None:
+        """Snapshot under the lock, then write beside the target and replace
+        it atomically. On OSError the temp file is removed and the error
+        raised."""
+        with self._lock:
+            snap = {"rv": self._rv, "objects": list(self._objects.values())}
+        d = os.path.dirname(os.path.abspath(self._persist_path)) or "."
+        fd, tmp = tempfile.mkstemp(dir=d, prefix=".store-")
+        try:
+            with os.fdopen(fd, "w") as f:
+                json.dump(snap, f)
+            os.replace(tmp, self._persist_path)  # atomic
+        except OSError:
+            try:
+                os.unlink(tmp)
+            except OSError:
+                pass
+            raise
 
+    def _persist_loop(self) -> None:
         while not self._persist_stop.is_set():
             if not self._persist_pending.wait(timeout=0.5):
                 continue
             # debounce: batch bursts of mutations into one write
             self._persist_stop.wait(self._persist_debounce_s)
             self._persist_pending.clear()
-            with self._lock:
-                snap = {"rv": self._rv, "objects": list(self._objects.values())}
-            d = os.path.dirname(os.path.abspath(self._persist_path)) or "."
-            fd, tmp = tempfile.mkstemp(dir=d, prefix=".store-")
             try:
-                with os.fdopen(fd, "w") as f:
-                    json.dump(snap, f)
-                os.replace(tmp, self._persist_path)  # atomic
+                self._write_snapshot()
             except OSError:
-                try:
-                    os.unlink(tmp)
-                except OSError:
-                    pass
+                pass  # write-behind: the next mutation tries again
 
     def flush(self) -> None:
         """Force one synchronous snapshot (tests / clean shutdown)."""
-        if not self._persist_path:
-            return
-        import os
-        import tempfile
-
-        with self._lock:
-            snap = {"rv": self._rv, "objects": list(self._objects.values())}
-        d = os.path.dirname(os.path.abspath(self._persist_path)) or "."
-        fd, tmp = tempfile.mkstemp(dir=d, prefix=".store-")
-        with os.fdopen(fd, "w") as f:
-            json.dump(snap, f)
-        os.replace(tmp, self._persist_path)
+        if self._persist_path:
+            self._write_snapshot()
 
     def close(self) -> None:
         self._persist_stop.set()
@@ -389,24 +473,29 @@ class MemStore:
                     f"{k}: resourceVersion {sent_rv} != {cur['metadata']['resourceVersion']}"
                 )
             obj = _snapshot(obj)
-            self._rv += 1
-            obj["metadata"]["resourceVersion"] = str(self._rv)
             # deletionTimestamp is sticky (k8s semantics)
             if cur["metadata"].get("deletionTimestamp") and not obj["metadata"].get(
                 "deletionTimestamp"
             ):
                 obj["metadata"]["deletionTimestamp"] = cur["metadata"]["deletionTimestamp"]
-            self._objects[k] = obj
-            # finalizer-free object already marked deleted -> actually remove
-            if obj["metadata"].get("deletionTimestamp") and not obj["metadata"].get(
-                "finalizers"
-            ):
-                del self._objects[k]
-                self._notify("DELETED", obj)
-            else:
-                self._notify("MODIFIED", obj)
-            self._mark_dirty()
+            self._commit(k, obj)
             return _snapshot(obj)
+
+    def _commit(self, k: Key, obj: dict) -> None:
+        """The tail of update and patch: stamp a fresh resourceVersion, then
+        replace the stored object and notify. Caller holds the lock."""
+        self._rv += 1
+        obj["metadata"]["resourceVersion"] = str(self._rv)
+        # finalizer-free object already marked deleted -> actually remove
+        if obj["metadata"].get("deletionTimestamp") and not obj["metadata"].get(
+            "finalizers"
+        ):
+            del self._objects[k]
+            self._notify("DELETED", obj)
+        else:
+            self._objects[k] = obj
+            self._notify("MODIFIED", obj)
+        self._mark_dirty()
 
     def delete(self, kind: str, name: str, namespace: str = "", *, now: float = 0.0) -> None:
         """k8s-style delete: with finalizers present, only sets
@@ -418,8 +507,6 @@ class MemStore:
             obj = self._objects[k]
             if obj["metadata"].get("finalizers"):
                 if not obj["metadata"].get("deletionTimestamp"):
-                    import time
-
                     obj["metadata"]["deletionTimestamp"] = now or time.time()
                     self._rv += 1
                     obj["metadata"]["resourceVersion"] = str(self._rv)
@@ -450,47 +537,8 @@ class MemStore:
                 raise NotFound(f"{k} not found")
             obj = _snapshot(self._objects[k])
             apply_patch_ops(obj, ops or [])
-            self._rv += 1
-            obj["metadata"]["resourceVersion"] = str(self._rv)
-            self._objects[k] = obj
-            if obj["metadata"].get("deletionTimestamp") and not obj["metadata"].get(
-                "finalizers"
-            ):
-                del self._objects[k]
-                self._notify("DELETED", obj)
-            else:
-                self._notify("MODIFIED", obj)
-            self._mark_dirty()
+            self._commit(k, obj)
             return None if quiet else _snapshot(obj)
-
-    def batch(self, requests: List[dict], *, quiet: bool = False) -> List[dict]:
-        """Execute several verbs in one call; per-entry results so callers
-        keep the same error semantics as individual calls. Over the TCP store
-        this collapses the agent's serial create-path writes (ConfigMap +
-        Node capacity + CR commit) into a single round-trip."""
-        out: List[dict] = []
-        for req in requests:
-            verb = req.get("verb")
-            try:
-                if verb == "create":
-                    res = self.create(req["obj"])
-                elif verb == "get":
-                    res = self.get(req["kind"], req["name"], req.get("namespace", ""))
-                elif verb == "update":
-                    res = self.update(req["obj"])
-                elif verb == "delete":
-                    self.delete(req["kind"], req["name"], req.get("namespace", ""))
-                    res = None
-                elif verb == "patch":
-                    res = self.patch(req["kind"], req["name"],
-                                     req.get("namespace", ""), req.get("ops"))
-                else:
-                    raise ValueError(f"unknown batch verb {verb!r}")
-                out.append({"ok": True, "result": None if quiet else res})
-            except (Conflict, NotFound, AlreadyExists) as e:
-                out.append({"ok": False, "result": None,
-                            "error": {"type": type(e).__name__, "msg": str(e)}})
-        return out
 
     # -- watch ------------------------------------------------------------
 
@@ -510,7 +558,7 @@ class MemStore:
         consumers absorb the duplicates); `w.resumed` says which happened
         and `w.rev` is the store revision at subscribe time."""
         with self._lock:
-            w = Watch(self, kind, filters)
+            w = Watch(kind, filters)
             w.rev = self._rv
             w.resumed = False
             if since is not None:
@@ -521,12 +569,12 @@ class MemStore:
                 if covered:
                     for ev_rv, et, o in self._history:
                         if ev_rv > since and w._matches(o):
-                            w._push((et, _snapshot(o)))
+                            w._deliver((et, _snapshot(o)))
                     w.resumed = True
             if replay and not w.resumed:
                 for _, o in sorted(self._objects.items()):
                     if w._matches(o):
-                        w._push(("ADDED", _snapshot(o)))
+                        w._deliver(("ADDED", _snapshot(o)))
             self._watches.append(w)
             return w
 
@@ -546,32 +594,4 @@ class MemStore:
             if w._matches(obj):
                 if snap is None:
                     snap = _snapshot(obj)
-                w._push((event_type, snap))
-
-    # -- helpers ----------------------------------------------------------
-
-    def update_with_retry(
-        self, kind: str, name: str, namespace: str, mutate: Callable[[dict], Optional[dict]],
-        attempts: int = 10,
-    ) -> Optional[dict]:
-        """Get-mutate-update loop absorbing Conflicts. `mutate` returns the
-        modified object or None to abort. This is the pattern the reference
-        implements as requeue-on-conflict (instaslice_controller.go:93)."""
-        for attempt in range(attempts):
-            try:
-                obj = self.get(kind, name, namespace)
-            except NotFound:
-                return None
-            new = mutate(obj)
-            if new is None:
-                return None
-            try:
-                return self.update(new)
-            except Conflict:
-                if attempt >= 2:  # hot object: jittered backoff breaks livelock
-                    import random
-                    import time as _time
-
-                    _time.sleep(random.random() * 0.002 * attempt)
-                continue
-        raise Conflict(f"update_with_retry: {attempts} attempts exhausted for {kind}/{name}")
+                w._deliver((event_type, snap))

@@ -27,13 +27,12 @@ from __future__ import annotations
 
 import atexit
 import os
-import queue
 import socket
 import socketserver
 import struct
 import threading
 import weakref
-from typing import Callable, List, Optional, Tuple
+from typing import List, Optional
 
 import msgpack
 
@@ -42,6 +41,9 @@ from instaslice_amd.store.memstore import (
     Conflict,
     MemStore,
     NotFound,
+    StoreVerbs,
+    WatchQueue,
+    execute,
 )
 from instaslice_amd.utils import get_logger
 
@@ -74,29 +76,6 @@ def _read_msg(rfile) -> Optional[dict]:
     if len(payload) < n:
         return None
     return msgpack.unpackb(payload, raw=False)
-
-
-def _execute(store: MemStore, req: dict):
-    """Dispatch one request dict onto the store (shared by the single-verb
-    path and batch)."""
-    verb = req.get("verb")
-    if verb == "create":
-        return store.create(req["obj"])
-    if verb == "get":
-        return store.get(req["kind"], req["name"], req.get("namespace", ""))
-    if verb == "list":
-        return store.list(req["kind"], req.get("namespace"))
-    if verb == "update":
-        return store.update(req["obj"])
-    if verb == "delete":
-        store.delete(req["kind"], req["name"], req.get("namespace", ""))
-        return None
-    if verb == "patch":
-        return store.patch(req["kind"], req["name"], req.get("namespace", ""),
-                           req.get("ops"))
-    if verb == "ping":
-        return "pong"
-    raise ValueError(f"unknown verb {verb!r}")
 
 
 class _Handler(socketserver.StreamRequestHandler):
@@ -163,7 +142,7 @@ class _Handler(socketserver.StreamRequestHandler):
                         ).start()
                         continue
                     else:
-                        res = _execute(store, req)
+                        res = execute(store, req)
                         if quiet:
                             res = None
                     send({"id": rid, "ok": True, "result": res})
@@ -209,64 +188,24 @@ class StoreServer:
         self._srv.server_close()
 
 
-class _ClientWatch:
-    """Client-side watch mirroring memstore.Watch (incl. push-mode
-    set_callback — see memstore.Watch.set_callback for the contract)."""
+class _ClientWatch(WatchQueue):
+    """Client-side watch: the shared queue plus the resume token."""
 
     def __init__(self) -> None:
-        self._q: "queue.Queue[Optional[Tuple[str, dict]]]" = queue.Queue()
-        self._stopped = False
-        self.kind: Optional[str] = None
-        self._cb = None
-        self._cb_lock = threading.Lock()
+        super().__init__()
         # highest event resourceVersion seen — the watch RESUME TOKEN a
         # reconnect passes as `since` so missed events replay without a
         # full relist (None until the subscribe response seeds it)
         self.last_rev: Optional[int] = None
 
-    def set_callback(self, fn) -> None:
-        with self._cb_lock:
-            while True:
-                try:
-                    ev = self._q.get_nowait()
-                except queue.Empty:
-                    break
-                if ev is not None:
-                    fn(*ev)
-            self._cb = fn
-
     def _deliver(self, event) -> None:
-        if self._stopped:
-            return
         try:
             rv = int(event[1]["metadata"]["resourceVersion"])
             if self.last_rev is None or rv > self.last_rev:
                 self.last_rev = rv
         except (KeyError, TypeError, ValueError, IndexError):
             pass
-        with self._cb_lock:
-            if self._cb is not None:
-                try:
-                    self._cb(*event)
-                except Exception:  # noqa: BLE001 - consumer bug must not kill reader
-                    import traceback
-
-                    traceback.print_exc()
-                return
-            # under the lock: a set_callback draining the queue right now
-            # must either see this event or have installed its callback
-            # before we looked — queued behind the drain it would be lost
-            self._q.put(event)
-
-    def next(self, timeout: Optional[float] = None) -> Optional[Tuple[str, dict]]:
-        try:
-            return self._q.get(timeout=timeout)
-        except queue.Empty:
-            return None
-
-    def stop(self) -> None:
-        self._stopped = True
-        self._q.put(None)
+        super()._deliver(event)
 
 
 def _native_wire_enabled() -> bool:
@@ -289,7 +228,7 @@ def _close_live_wires() -> None:
             pass
 
 
-class NetStoreClient:
+class NetStoreClient(StoreVerbs):
     """Store client with the MemStore interface (duck-typed).
 
     Without reconnect, and when the _netwire extension is built (and
@@ -569,29 +508,6 @@ class NetStoreClient:
         for ev in orphans:
             w._deliver(ev)
         return w
-
-    def update_with_retry(
-        self, kind: str, name: str, namespace: str,
-        mutate: Callable[[dict], Optional[dict]], attempts: int = 25,
-    ) -> Optional[dict]:
-        for attempt in range(attempts):
-            try:
-                obj = self.get(kind, name, namespace)
-            except NotFound:
-                return None
-            new = mutate(obj)
-            if new is None:
-                return None
-            try:
-                return self.update(new)
-            except Conflict:
-                if attempt >= 2:  # hot object: jittered backoff breaks livelock
-                    import random
-                    import time as _time
-
-                    _time.sleep(random.random() * 0.002 * attempt)
-                continue
-        raise Conflict(f"update_with_retry: {attempts} attempts exhausted for {kind}/{name}")
 
     def close(self) -> None:
         self._closed = True

@@ -184,8 +184,9 @@ def test_batch_partial_failure_shapes(store):
          "namespace": INSTASLICE_NS, "ops": [
              {"op": "set", "path": ["spec", "cordoned"], "value": True}]},
     ], quiet=True)
-    assert res[0]["ok"]
+    assert res[0]["ok"] and res[0]["result"] is None  # quiet
     assert not res[1]["ok"] and res[1]["error"]["type"] == "Conflict"
+    assert res[1]["result"] is None
     assert not res[2]["ok"] and res[2]["error"]["type"] == "NotFound"
     assert res[3]["ok"]  # later requests still ran (sequential, not aborted)
     assert store.get("Instaslice", "node-0", INSTASLICE_NS)["spec"]["cordoned"]

@@ -145,6 +145,10 @@ def test_batch_and_quiet(client):
     assert client.patch("Thing", "b1", "",
                         [{"op": "set", "path": ["spec", "v"], "value": 9}],
                         quiet=True) is None
+    res = client.batch([{"verb": "list", "kind": "Thing"}, {"verb": "ping"}])
+    assert [r["ok"] for r in res] == [True, True]
+    assert [o["metadata"]["name"] for o in res[0]["result"]] == ["b1"]
+    assert res[1]["result"] == "pong"
 
 
 def test_watch_kinds_replay_and_filters(client):

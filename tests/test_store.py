@@ -92,6 +92,34 @@ def test_watch_kind_filter():
     assert obj["kind"] == "Pod"
 
 
+def test_event_racing_set_callback_is_not_stranded():
+    """A mutating thread that found no callback must not enqueue behind
+    set_callback's drain: the queue is never read again after that. The
+    queue's put is held back until set_callback has returned (or, with the
+    put under the watch's lock, until set_callback is blocked on it)."""
+    s = MemStore()
+    w = s.watch("Thing", replay=False)
+    at_put, release = threading.Event(), threading.Event()
+    real_put = w._q.put
+
+    def slow_put(item):
+        at_put.set()
+        release.wait(0.5)
+        real_put(item)
+
+    w._q.put = slow_put
+    t = threading.Thread(target=s.create, args=(_obj("a"),))
+    t.start()
+    assert at_put.wait(5)
+    got = []
+    w.set_callback(lambda et, obj: got.append((et, obj["metadata"]["name"])))
+    release.set()
+    t.join(5)
+    assert not t.is_alive()
+    assert got == [("ADDED", "a")]
+    assert w._q.empty()
+
+
 def test_update_with_retry_absorbs_conflicts():
     s = MemStore()
     s.create(_obj("a", n=0))
