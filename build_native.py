@@ -81,18 +81,19 @@ def build(force: bool = False) -> None:
 
     # 1. _partitiond pybind module (host-only C++, links libamd_smi)
     src = smi_dir / "csrc" / "partitiond_pybind.cpp"
-    hdr = smi_dir / "csrc" / "partitiond_core.hpp"
+    hdrs = [smi_dir / "csrc" / h for h in
+            ("partitiond_core.hpp", "partitiond_metrics.hpp")]
     out = smi_dir / f"_partitiond{EXT}"
-    if force or not newer(out, [src, hdr], "pybind"):
+    if force or not newer(out, [src, *hdrs], "pybind"):
         run([CLANGXX, "-shared", *common, *pybind_includes(), src, "-lamd_smi", "-o", out])
-        record_hash(out, [src, hdr], "pybind")
+        record_hash(out, [src, *hdrs], "pybind")
 
     # 2. partitiond standalone daemon
     src = smi_dir / "csrc" / "partitiond_main.cpp"
     out = bin_dir / "partitiond"
-    if force or not newer(out, [src, hdr], "daemon"):
+    if force or not newer(out, [src, *hdrs], "daemon"):
         run([CLANGXX, *common, src, "-lamd_smi", "-o", out])
-        record_hash(out, [src, hdr], "daemon")
+        record_hash(out, [src, *hdrs], "daemon")
 
     # 3. _payload pybind module (gfx950 device code)
     src = ops_dir / "csrc" / "payload_pybind.hip"

@@ -23,6 +23,8 @@
 #include <string>
 #include <vector>
 
+#include "partitiond_metrics.hpp"
+
 namespace partitiond {
 
 struct SmiException : std::runtime_error {
@@ -60,11 +62,20 @@ struct ProfileInfo {
   std::vector<std::string> memory_caps;  // "NPS1"...
 };
 
-struct Metrics {
-  double gfx_activity_pct = -1;
-  double umc_activity_pct = -1;
-  double vram_used_mb = -1;
-  double socket_power_w = -1;
+// The api read_metrics() runs on outside the self-test: libamd_smi itself.
+struct AmdSmiMetricsApi {
+  amdsmi_status_t metrics_info(amdsmi_processor_handle h, amdsmi_gpu_metrics_t* t) {
+    return amdsmi_get_gpu_metrics_info(h, t);
+  }
+  amdsmi_status_t memory_usage(amdsmi_processor_handle h, uint64_t* used) {
+    return amdsmi_get_gpu_memory_usage(h, AMDSMI_MEM_TYPE_VRAM, used);
+  }
+  amdsmi_status_t activity(amdsmi_processor_handle h, amdsmi_engine_usage_t* u) {
+    return amdsmi_get_gpu_activity(h, u);
+  }
+  amdsmi_status_t power_info(amdsmi_processor_handle h, amdsmi_power_info_t* p) {
+    return amdsmi_get_power_info(h, p);
+  }
 };
 
 inline const char* compute_mode_name(amdsmi_compute_partition_type_t t) {
@@ -115,6 +126,7 @@ class Partitiond {
     amdsmi_shut_down();
     initialized_ = false;
     handles_.clear();
+    samples_.invalidate();
   }
 
   // Re-walk sockets/processors. Called once at agent boot and after each
@@ -146,7 +158,7 @@ class Partitiond {
                                            compute_mode_from_name(mode)),
           "amdsmi_set_gpu_compute_partition");
     // handle population may have changed; force re-walk on next enumerate
-    stale_ = true;
+    mode_changed_locked();
   }
 
   std::string get_memory_partition(uint32_t index) {
@@ -164,7 +176,7 @@ class Partitiond {
     check(amdsmi_set_gpu_memory_partition(handle_locked(index),
                                           memory_mode_from_name(mode)),
           "amdsmi_set_gpu_memory_partition");
-    stale_ = true;
+    mode_changed_locked();
   }
 
   // The MODE-based memory set (amdsmi.h:5920) — distinct entry point from
@@ -175,7 +187,7 @@ class Partitiond {
     check(amdsmi_set_gpu_memory_partition_mode(handle_locked(index),
                                                memory_mode_from_name(mode)),
           "amdsmi_set_gpu_memory_partition_mode");
-    stale_ = true;
+    mode_changed_locked();
   }
 
   // Accelerator-partition profile catalog (amdsmi.h:5950); the MI355X analog
@@ -245,7 +257,7 @@ class Partitiond {
     std::lock_guard<std::mutex> lk(mu_);
     check(amdsmi_set_gpu_accelerator_partition_profile(handle_locked(index), profile_index),
           "amdsmi_set_gpu_accelerator_partition_profile");
-    stale_ = true;
+    mode_changed_locked();
   }
 
   // Pairwise link topology (amdsmi_topo_get_link_type/_weight, amdsmi.h:5635,
@@ -293,28 +305,23 @@ class Partitiond {
   }
 
   // Counters captured around every reconfigure (north-star observability).
-  Metrics get_metrics(uint32_t index) {
+  // A sample younger than max_age_ms is handed out again without touching
+  // the device or mu_; 0 always reads. Every mode set drops the samples, so
+  // the first read after one is fresh.
+  Metrics get_metrics(uint32_t index, int64_t max_age_ms = kMetricsMaxAgeMs) {
+    return samples_.get_or_read(index, max_age_ms, [&] {
+      std::lock_guard<std::mutex> lk(mu_);
+      AmdSmiMetricsApi api;
+      return read_metrics(handle_locked(index), api);
+    });
+  }
+
+  // The sample by the three per-call sources, uncached (see
+  // read_metrics_by_calls).
+  Metrics get_metrics_by_calls(uint32_t index) {
     std::lock_guard<std::mutex> lk(mu_);
-    Metrics m;
-    amdsmi_processor_handle h = handle_locked(index);
-    amdsmi_engine_usage_t usage;
-    if (amdsmi_get_gpu_activity(h, &usage) == AMDSMI_STATUS_SUCCESS) {
-      if (usage.gfx_activity != UINT32_MAX) m.gfx_activity_pct = usage.gfx_activity;
-      if (usage.umc_activity != UINT32_MAX) m.umc_activity_pct = usage.umc_activity;
-    }
-    uint64_t used = 0;
-    if (amdsmi_get_gpu_memory_usage(h, AMDSMI_MEM_TYPE_VRAM, &used) ==
-        AMDSMI_STATUS_SUCCESS) {
-      m.vram_used_mb = static_cast<double>(used) / (1024.0 * 1024.0);
-    }
-    amdsmi_power_info_t power;
-    if (amdsmi_get_power_info(h, &power) == AMDSMI_STATUS_SUCCESS) {
-      if (power.socket_power != UINT64_MAX && power.socket_power != 0)
-        m.socket_power_w = static_cast<double>(power.socket_power);
-      else if (power.current_socket_power != UINT32_MAX)
-        m.socket_power_w = power.current_socket_power;
-    }
-    return m;
+    AmdSmiMetricsApi api;
+    return read_metrics_by_calls(handle_locked(index), api);
   }
 
   size_t num_processors() {
@@ -347,6 +354,11 @@ class Partitiond {
       for (auto p : procs) handles_.push_back(p);
     }
     stale_ = false;
+  }
+
+  void mode_changed_locked() {
+    stale_ = true;
+    samples_.invalidate();
   }
 
   amdsmi_processor_handle handle_locked(uint32_t index) {
@@ -406,6 +418,7 @@ class Partitiond {
   bool initialized_ = false;
   bool stale_ = false;
   std::vector<amdsmi_processor_handle> handles_;
+  MetricsCache<> samples_;
 };
 
 }  // namespace partitiond

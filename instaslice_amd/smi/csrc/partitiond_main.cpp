@@ -9,7 +9,7 @@
 //   get_compute <idx> | set_compute <idx> <SPX|DPX|QPX|CPX>
 //   get_memory <idx>  | set_memory <idx> <NPS1|NPS2|NPS4>
 //   profiles <idx>    | set_profile <idx> <profile_index>
-//   current_profile <idx> | topology | metrics <idx> | quit
+//   current_profile <idx> | topology | metrics <idx> [max_age_ms] | quit
 //
 // Build: see build_native.py (amdclang++ -lamd_smi).
 
@@ -140,7 +140,9 @@ int main() {
         reply_ok(o.str());
       } else if (verb == "metrics") {
         uint32_t idx; iss >> idx;
-        Metrics mt = d.get_metrics(idx);
+        int64_t max_age_ms;
+        if (!(iss >> max_age_ms)) max_age_ms = kMetricsMaxAgeMs;
+        Metrics mt = d.get_metrics(idx, max_age_ms);
         std::ostringstream o;
         o << "{\"gfx_activity_pct\": " << mt.gfx_activity_pct
           << ", \"umc_activity_pct\": " << mt.umc_activity_pct

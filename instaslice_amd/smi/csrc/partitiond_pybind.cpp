@@ -85,7 +85,10 @@ PYBIND11_MODULE(_partitiond, m) {
            py::call_guard<py::gil_scoped_release>())
       .def("get_link_topology", &Partitiond::get_link_topology,
            py::call_guard<py::gil_scoped_release>())
-      .def("get_metrics", &Partitiond::get_metrics,
+      .def("get_metrics", &Partitiond::get_metrics, py::arg("index"),
+           py::arg("max_age_ms") = kMetricsMaxAgeMs,
+           py::call_guard<py::gil_scoped_release>())
+      .def("get_metrics_by_calls", &Partitiond::get_metrics_by_calls,
            py::call_guard<py::gil_scoped_release>());
 
   // amdsmi status codes Python needs to classify failures
