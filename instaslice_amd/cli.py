@@ -19,8 +19,8 @@
     python -m instaslice_amd top        --store HOST:PORT [--interval S]
     python -m instaslice_amd cordon     --store HOST:PORT --node N [--uncordon]
     python -m instaslice_amd payload    [info|vecadd|membw|busy|census|gemm|
-                                         mxgemm|mx4gemm|attn|prefill|memcheck|
-                                         verify] ...
+                                         dgemm|mxgemm|mx4gemm|attn|prefill|
+                                         memcheck|verify] ...
     python -m instaslice_amd verify     --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
     python -m instaslice_amd memcheck   --profile NAME [--gb G | --fraction F]
@@ -30,9 +30,11 @@
                                         [--visible-devices UUID_OR_INDEX]
     python -m instaslice_amd mx4gemm    --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
+    python -m instaslice_amd dgemm      --profile NAME
+                                        [--visible-devices UUID_OR_INDEX]
     python -m instaslice_amd attn       --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
-    python -m instaslice_amd prefill    --profile NAME
+    python -m instaslice_amd prefill   --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
 
 NODE_NAME env is honored for the daemonset (downward-API parity with
@@ -420,6 +422,13 @@ def cmd_mx4gemm(args) -> int:
     return _probe(args, "run_mx4gemm")
 
 
+def cmd_dgemm(args) -> int:
+    """Run the FP64 MFMA GEMM payload inside the visible partition and judge
+    it against the requested profile; prints the judged JSON, exit 0 iff
+    ok."""
+    return _probe(args, "run_dgemm")
+
+
 def cmd_attn(args) -> int:
     """Run the KV-cache decode attention payload inside the visible partition
     and judge it against the requested profile; prints the judged JSON, exit
@@ -575,6 +584,15 @@ def main(argv=None) -> int:
                    help="ROCR_VISIBLE_DEVICES for the probe (partition UUID "
                         "or index); default: inherit the environment")
     p.set_defaults(fn=cmd_mx4gemm)
+
+    p = sub.add_parser("dgemm",
+                       help="exact-check and time the FP64 matrix path of the "
+                            "visible partition, judge it against a profile")
+    p.add_argument("--profile", required=True, help="e.g. cpx-1x36")
+    p.add_argument("--visible-devices", default=None,
+                   help="ROCR_VISIBLE_DEVICES for the probe (partition UUID "
+                        "or index); default: inherit the environment")
+    p.set_defaults(fn=cmd_dgemm)
 
     p = sub.add_parser("attn",
                        help="check and time KV-cache decode attention (the "

@@ -21,6 +21,11 @@
 //                correctness dependency — cdna_hip_programming.md §1.)
 //   gemm         bf16 MFMA GEMM, exact-checked and timed: the matrix cores are
 //                what a tenant pays for (payload_gemm.hpp, included below)
+//   dgemm        FP64 MFMA GEMM (v_mfma_f64_16x16x4_f64, fp64 operands and
+//                accumulation), exact-checked on a pattern that needs all of
+//                fp64 and timed: the double-precision matrix path an HPC
+//                tenant runs on, an instruction, operand width and accumulator
+//                layout of its own (payload_dgemm.hpp, included below)
 //   mxgemm       MXFP8 block-scaled MFMA GEMM (OCP e4m3 operands, E8M0 scales
 //                per 32 elements), exact-checked and timed: the low-precision
 //                matrix path, a different instruction and datapath than bf16
@@ -574,6 +579,10 @@ inline int device_count() {
 // bf16 MFMA GEMM payload: uses HIP_CHECK, kBlock and the detail helpers from
 // above, detail::time_launches among them
 #include "payload_gemm.hpp"
+
+// FP64 MFMA GEMM payload: the bf16 one's LDS offset rule, GemmShape, drivers
+// and integer pattern
+#include "payload_dgemm.hpp"
 
 // MXFP8 block-scaled MFMA GEMM payload: same helpers, plus the gemm pattern
 #include "payload_mxgemm.hpp"

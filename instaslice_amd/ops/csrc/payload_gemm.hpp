@@ -164,7 +164,7 @@ namespace detail {
 
 inline size_t round_up(size_t v, size_t m) { return (v + m - 1) / m * m; }
 
-// What the three GEMM payloads' problems share: the shape, the padded shape
+// What the GEMM payloads' problems share: the shape, the padded shape
 // and the padded C. Each problem adds its padded operands, upload() and
 // launch().
 struct GemmShape {
@@ -185,15 +185,16 @@ struct GemmShape {
       throw std::invalid_argument(who + ": shape too large");
   }
 
-  // grid = (Np / 128, Mp / 128) for all three kernels
+  // grid = (Np / 128, Mp / 128) for every GEMM kernel
   dim3 grid() const {
     return dim3(static_cast<unsigned>(Np / kGemmBN), static_cast<unsigned>(Mp / kGemmBM));
   }
 
-  // the un-padded M x N region, row-major, into c
-  void download(float* c) const {
-    HIP_CHECK(hipMemcpy2D(c, static_cast<size_t>(N) * sizeof(float), dc.p,
-                          Np * sizeof(float), static_cast<size_t>(N) * sizeof(float),
+  // the un-padded M x N region, row-major, into c; T is C's element type
+  template <class T>
+  void download(T* c) const {
+    HIP_CHECK(hipMemcpy2D(c, static_cast<size_t>(N) * sizeof(T), dc.p,
+                          Np * sizeof(T), static_cast<size_t>(N) * sizeof(T),
                           M, hipMemcpyDeviceToHost));
   }
 };
@@ -267,13 +268,15 @@ inline void require_exact_k(int k, const char* who) {
 }
 
 // The three drivers below serve every GEMM payload. P is a problem: a
-// GemmShape with upload(device) and launch(). PatternErr is |got - exact| of
-// output (i, j) of the problem's own pattern at depth K.
-using PatternErr = double (*)(float got, int i, int j, int K);
+// GemmShape with upload(device) and launch(). T is the element type of its C
+// (float, or double for dgemm), deduced from the call. PatternErr is
+// |got - exact| of output (i, j) of the problem's own pattern at depth K.
+template <class T>
+using PatternErr = double (*)(T got, int i, int j, int K);
 
 // upload, one launch, the M x N result into c
-template <class P>
-void run_once(P& p, int device, float* c) {
+template <class P, class T>
+void run_once(P& p, int device, T* c) {
   p.upload(device);
   p.launch();
   HIP_CHECK(hipGetLastError());
@@ -281,9 +284,9 @@ void run_once(P& p, int device, float* c) {
 }
 
 // max err over the whole M x N result of a problem filled with its pattern
-template <class P>
-double run_full_check(P& p, int device, PatternErr err) {
-  std::vector<float> host(static_cast<size_t>(p.M) * p.N);
+template <class P, class T>
+double run_full_check(P& p, int device, PatternErr<T> err) {
+  std::vector<T> host(static_cast<size_t>(p.M) * p.N);
   run_once(p, device, host.data());
   double max_err = 0;
   for (int i = 0; i < p.M; ++i)
@@ -295,8 +298,8 @@ double run_full_check(P& p, int device, PatternErr err) {
 // One warm-up launch, `iters` launches between events, then 256 fixed, spread
 // output elements are checked exactly, so a fast wrong kernel cannot report a
 // rate. FLOPs are counted as 2 M N K.
-template <class P>
-GemmResult run_timed(P& p, int iters, int device, PatternErr err) {
+template <class P, class T>
+GemmResult run_timed(P& p, int iters, int device, PatternErr<T> err) {
   p.upload(device);
   const float ms = time_launches(iters, [&p] { p.launch(); });
   GemmResult r;
@@ -304,9 +307,9 @@ GemmResult run_timed(P& p, int iters, int device, PatternErr err) {
   for (int t = 0; t < 256; ++t) {
     int i = static_cast<int>((static_cast<int64_t>(t) * 1031 + 17) % p.M);
     int j = static_cast<int>((static_cast<int64_t>(t) * 2053 + 29) % p.N);
-    float got = 0;
-    HIP_CHECK(hipMemcpy(&got, p.dc.template as<float>() + static_cast<size_t>(i) * p.Np + j,
-                        sizeof(float), hipMemcpyDeviceToHost));
+    T got = 0;
+    HIP_CHECK(hipMemcpy(&got, p.dc.template as<T>() + static_cast<size_t>(i) * p.Np + j,
+                        sizeof(T), hipMemcpyDeviceToHost));
     note_err(r.max_err, err(got, i, j, p.K));
   }
   return r;

@@ -21,6 +21,12 @@
 //                                             and timed (default 4096 4096
 //                                             1024, 10 iters; K <= 1024);
 //                                             exit 1 unless max_err == 0
+//   instaslice-payload dgemm [M N K [ITERS]]  FP64 MFMA GEMM (fp64 operands
+//                                             and accumulation), exact-checked
+//                                             on a 2^-16-scaled integer pattern
+//                                             and timed (default 4096 4096
+//                                             1024, 10 iters; K <= 65536);
+//                                             exit 1 unless max_err == 0
 //   instaslice-payload mxgemm [M N K [ITERS]] MXFP8 block-scaled MFMA GEMM
 //                                             (e4m3 operands, E8M0 scales per
 //                                             32 elements), exact-checked and
@@ -144,7 +150,7 @@ static bool print_memcheck(const MemcheckResult& r) {
   return ok;
 }
 
-// the three GEMM payloads share their verbs' arguments and report lines
+// the GEMM payloads share their verbs' arguments and report lines
 struct GemmVerb {
   const char* name;
   GemmResult (*run)(int m, int n, int k, int iters, int device);
@@ -154,6 +160,7 @@ struct GemmVerb {
 
 static const GemmVerb kGemmVerbs[] = {
     {"gemm", run_gemm, run_gemm_check, 1024},
+    {"dgemm", run_dgemm, run_dgemm_check, 1024},
     {"mxgemm", run_mxgemm, run_mxgemm_check, 2048},
     {"mx4gemm", run_mx4gemm, run_mx4gemm_check, 2048},
 };
@@ -362,9 +369,9 @@ int main(int argc, char** argv) {
       return ok ? 0 : 1;
     } else if (std::strcmp(cmd, "serve") == 0) {
       // warm-pool worker: one line per request, one JSON line per reply
-      //   vecadd <n> | busy <ms> | gemm [M N K] | mxgemm [M N K] |
-      //   mx4gemm [M N K] | attn [B HQ HKV L] | prefill [B HQ HKV L] |
-      //   memcheck [BYTES] | ping | quit
+      //   vecadd <n> | busy <ms> | gemm [M N K] | dgemm [M N K] |
+      //   mxgemm [M N K] | mx4gemm [M N K] | attn [B HQ HKV L] |
+      //   prefill [B HQ HKV L] | memcheck [BYTES] | ping | quit
       std::string line;
       while (std::getline(std::cin, line)) {
         std::istringstream iss(line);

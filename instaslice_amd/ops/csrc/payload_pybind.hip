@@ -21,6 +21,7 @@ namespace {
 template <class T>
 using c_array = py::array_t<T, py::array::c_style | py::array::forcecast>;
 using f32_array = c_array<float>;
+using f64_array = c_array<double>;
 using u32_array = c_array<uint32_t>;
 using u8_array = c_array<uint8_t>;
 
@@ -107,15 +108,18 @@ std::array<int, 3> gemm_dims(const char* who, const py::array& a, const py::arra
                             static_cast<int>(a.shape(1))};
 }
 
-// C (M,N) of one of the general GEMM entries on float operands
-using GemmEntry = void (*)(const float*, const float*, float*, int, int, int, int);
-py::array_t<float> gemm_f32(const char* who, GemmEntry entry, const f32_array& a,
-                            const f32_array& b, int device) {
+// C (M,N) of one of the general GEMM entries on operands of element type T
+// (float, or double for gemm_f64)
+template <class T>
+using GemmEntry = void (*)(const T*, const T*, T*, int, int, int, int);
+template <class T>
+py::array_t<T> gemm_dense(const char* who, GemmEntry<T> entry, const c_array<T>& a,
+                          const c_array<T>& b, int device) {
   auto [M, N, K] = gemm_dims(who, a, b);
-  py::array_t<float> c({static_cast<py::ssize_t>(M), static_cast<py::ssize_t>(N)});
-  const float* pa = a.data();
-  const float* pb = b.data();
-  float* pc = c.mutable_data();
+  py::array_t<T> c({static_cast<py::ssize_t>(M), static_cast<py::ssize_t>(N)});
+  const T* pa = a.data();
+  const T* pb = b.data();
+  T* pc = c.mutable_data();
   {
     py::gil_scoped_release rel;
     entry(pa, pb, pc, M, N, K, device);
@@ -399,7 +403,7 @@ PYBIND11_MODULE(_payload, m) {
   m.def(
       "gemm_bf16",
       [](f32_array a, f32_array b, int device) {
-        return gemm_f32("gemm_bf16", payload::gemm_bf16, a, b, device);
+        return gemm_dense<float>("gemm_bf16", payload::gemm_bf16, a, b, device);
       },
       py::arg("a"), py::arg("b"), py::arg("device") = 0,
       "C (M,N) float32 = bf16(a (M,K)) @ bf16(b (K,N)) on the MFMA kernel");
@@ -422,6 +426,35 @@ PYBIND11_MODULE(_payload, m) {
       py::arg("m") = 4096, py::arg("n") = 4096, py::arg("k") = 1024,
       py::arg("iters") = 10, py::arg("device") = 0,
       "timed bf16 MFMA GEMM, 256 outputs spot-checked exactly; K <= 1024");
+
+  m.def(
+      "gemm_f64",
+      [](f64_array a, f64_array b, int device) {
+        return gemm_dense<double>("gemm_f64", payload::gemm_f64, a, b, device);
+      },
+      py::arg("a"), py::arg("b"), py::arg("device") = 0,
+      "C (M,N) float64 = a (M,K) @ b (K,N) with fp64 operands and accumulation on "
+      "the FP64 MFMA kernel; ValueError on a non-finite input");
+
+  m.def(
+      "run_dgemm_check",
+      [](int mm, int n, int k, int device) {
+        py::gil_scoped_release rel;
+        return payload::run_dgemm_check(mm, n, k, device);
+      },
+      py::arg("m"), py::arg("n"), py::arg("k"), py::arg("device") = 0,
+      "FP64 GEMM on an integer pattern scaled by 2^-16 (46-bit results at K = "
+      "1024) vs host int64 reference; returns max abs error (expect 0); "
+      "K <= 65536");
+
+  m.def(
+      "run_dgemm",
+      [](int mm, int n, int k, int iters, int device) {
+        return run_timed_gemm(payload::run_dgemm, mm, n, k, iters, device);
+      },
+      py::arg("m") = 4096, py::arg("n") = 4096, py::arg("k") = 1024,
+      py::arg("iters") = 10, py::arg("device") = 0,
+      "timed FP64 MFMA GEMM, 256 outputs spot-checked exactly; K <= 65536");
 
   m.def(
       "to_e4m3",
@@ -448,7 +481,7 @@ PYBIND11_MODULE(_payload, m) {
   m.def(
       "gemm_mxfp8",
       [](f32_array a, f32_array b, int device) {
-        return gemm_f32("gemm_mxfp8", payload::gemm_mxfp8, a, b, device);
+        return gemm_dense<float>("gemm_mxfp8", payload::gemm_mxfp8, a, b, device);
       },
       py::arg("a"), py::arg("b"), py::arg("device") = 0,
       "C (M,N) float32 = mx(a (M,K)) @ mx(b (K,N)): rows of a and columns of b "
@@ -537,7 +570,7 @@ PYBIND11_MODULE(_payload, m) {
   m.def(
       "gemm_mxfp4",
       [](f32_array a, f32_array b, int device) {
-        return gemm_f32("gemm_mxfp4", payload::gemm_mxfp4, a, b, device);
+        return gemm_dense<float>("gemm_mxfp4", payload::gemm_mxfp4, a, b, device);
       },
       py::arg("a"), py::arg("b"), py::arg("device") = 0,
       "C (M,N) float32 = mx4(a (M,K)) @ mx4(b (K,N)): rows of a and columns of b "

@@ -47,6 +47,16 @@ registers, at twice the MXFP8 rate per clock, so a partition can pass `mxgemm`
 and still be wrong or slow here. Its TFLOP/s is carried in the report and
 never judged.
 
+Double precision is a matrix path of its own. `run_dgemm` runs
+`instaslice-payload dgemm` (the FP64 MFMA GEMM: fp64 operands and
+accumulation on `v_mfma_f64_16x16x4_f64`, exact-checked and timed at 4096 x
+4096 x 1024 on an integer pattern scaled by 2**-16, whose results span 46
+bits) and `judge_dgemm` fails "dgemm" unless the maximum error is exactly
+zero: anything that multiplies or accumulates in less than fp64 gets a wrong
+answer, not a slightly different one. None of the other probes issues a
+double-precision instruction, so a partition can pass all of them and still
+fail here. Its TFLOP/s is carried in the report and never judged.
+
 So has the serving path. `run_attn` runs `instaslice-payload attn` (KV-cache
 decode attention: single-token grouped-query attention at head dim 128, K and
 V streamed through the bf16 MFMA with an fp32 online softmax and a split-KV
@@ -301,6 +311,29 @@ def run_mx4gemm(profile_name: str, env: Optional[Dict[str, str]] = None,
     parse_profile_name(profile_name)
     return _run_child(profile_name, ["mx4gemm"], CHILD_TIMEOUT_S, "max_err",
                       lambda report: judge_mx4gemm(report, profile_name),
+                      env, runner)
+
+
+# ---- dgemm ------------------------------------------------------------------
+
+def judge_dgemm(report: dict, profile_name: str) -> dict:
+    """Judge an `instaslice-payload dgemm` report: "dgemm" fails unless
+    `max_err` is a numeric zero and `m`, `n`, `k`, `iters` are integer counts
+    >= 1. `tflops` is carried and never judged. Pure; the report's own `ok`
+    is not trusted. ValueError on a profile name that does not parse."""
+    return _judge_one(report, profile_name, "dgemm", _mx_fields_clean)
+
+
+def run_dgemm(profile_name: str, env: Optional[Dict[str, str]] = None,
+              runner: Callable = subprocess.run) -> dict:
+    """Run `instaslice-payload dgemm` (default shape and iterations) in a
+    fresh child with `env` and judge its report, with the same contract as
+    `run_mxgemm`: every way the child can fail comes back as `ok: False`
+    with a `reason`, and only an unparseable profile name raises
+    (ValueError)."""
+    parse_profile_name(profile_name)
+    return _run_child(profile_name, ["dgemm"], CHILD_TIMEOUT_S, "max_err",
+                      lambda report: judge_dgemm(report, profile_name),
                       env, runner)
 
 
