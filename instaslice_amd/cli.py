@@ -19,8 +19,8 @@
     python -m instaslice_amd top        --store HOST:PORT [--interval S]
     python -m instaslice_amd cordon     --store HOST:PORT --node N [--uncordon]
     python -m instaslice_amd payload    [info|vecadd|membw|busy|census|gemm|
-                                         dgemm|mxgemm|mx4gemm|attn|prefill|
-                                         memcheck|verify] ...
+                                         dgemm|igemm|mxgemm|mx4gemm|attn|
+                                         prefill|memcheck|verify] ...
     python -m instaslice_amd verify     --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
     python -m instaslice_amd memcheck   --profile NAME [--gb G | --fraction F]
@@ -31,6 +31,8 @@
     python -m instaslice_amd mx4gemm    --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
     python -m instaslice_amd dgemm      --profile NAME
+                                        [--visible-devices UUID_OR_INDEX]
+    python -m instaslice_amd igemm      --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
     python -m instaslice_amd attn       --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
@@ -429,6 +431,13 @@ def cmd_dgemm(args) -> int:
     return _probe(args, "run_dgemm")
 
 
+def cmd_igemm(args) -> int:
+    """Run the INT8 MFMA GEMM payload inside the visible partition and judge
+    it against the requested profile; prints the judged JSON, exit 0 iff
+    ok."""
+    return _probe(args, "run_igemm")
+
+
 def cmd_attn(args) -> int:
     """Run the KV-cache decode attention payload inside the visible partition
     and judge it against the requested profile; prints the judged JSON, exit
@@ -593,6 +602,15 @@ def main(argv=None) -> int:
                    help="ROCR_VISIBLE_DEVICES for the probe (partition UUID "
                         "or index); default: inherit the environment")
     p.set_defaults(fn=cmd_dgemm)
+
+    p = sub.add_parser("igemm",
+                       help="exact-check and time the INT8 matrix path of the "
+                            "visible partition, judge it against a profile")
+    p.add_argument("--profile", required=True, help="e.g. cpx-1x36")
+    p.add_argument("--visible-devices", default=None,
+                   help="ROCR_VISIBLE_DEVICES for the probe (partition UUID "
+                        "or index); default: inherit the environment")
+    p.set_defaults(fn=cmd_igemm)
 
     p = sub.add_parser("attn",
                        help="check and time KV-cache decode attention (the "

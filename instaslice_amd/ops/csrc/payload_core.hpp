@@ -26,6 +26,12 @@
 //                fp64 and timed: the double-precision matrix path an HPC
 //                tenant runs on, an instruction, operand width and accumulator
 //                layout of its own (payload_dgemm.hpp, included below)
+//   igemm        INT8 MFMA GEMM (v_mfma_i32_32x32x32_i8, int32 accumulation),
+//                raw or with the W8A8 per-token and per-channel scales applied
+//                on the way out, exact-checked over the whole int8 range and
+//                timed: the integer matrix path a quantised inference tenant
+//                runs on, and the only GEMM on 32 x 32 tiles
+//                (payload_igemm.hpp, included below)
 //   mxgemm       MXFP8 block-scaled MFMA GEMM (OCP e4m3 operands, E8M0 scales
 //                per 32 elements), exact-checked and timed: the low-precision
 //                matrix path, a different instruction and datapath than bf16
@@ -583,6 +589,9 @@ inline int device_count() {
 // FP64 MFMA GEMM payload: the bf16 one's LDS offset rule, GemmShape, drivers
 // and integer pattern
 #include "payload_dgemm.hpp"
+
+// INT8 MFMA GEMM payload: the bf16 one's LDS offset rule, GemmShape and drivers
+#include "payload_igemm.hpp"
 
 // MXFP8 block-scaled MFMA GEMM payload: same helpers, plus the gemm pattern
 #include "payload_mxgemm.hpp"

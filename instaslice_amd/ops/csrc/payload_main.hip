@@ -27,6 +27,13 @@
 //                                             and timed (default 4096 4096
 //                                             1024, 10 iters; K <= 65536);
 //                                             exit 1 unless max_err == 0
+//   instaslice-payload igemm [M N K [ITERS]]  INT8 MFMA GEMM (int8 operands,
+//                                             int32 accumulation), exact-checked
+//                                             on a pattern over the whole int8
+//                                             range and timed (default 4096 4096
+//                                             4096, 10 iters; K <= 131071);
+//                                             "tflops" counts integer operations;
+//                                             exit 1 unless max_err == 0
 //   instaslice-payload mxgemm [M N K [ITERS]] MXFP8 block-scaled MFMA GEMM
 //                                             (e4m3 operands, E8M0 scales per
 //                                             32 elements), exact-checked and
@@ -161,6 +168,7 @@ struct GemmVerb {
 static const GemmVerb kGemmVerbs[] = {
     {"gemm", run_gemm, run_gemm_check, 1024},
     {"dgemm", run_dgemm, run_dgemm_check, 1024},
+    {"igemm", run_igemm, run_igemm_check, 4096},
     {"mxgemm", run_mxgemm, run_mxgemm_check, 2048},
     {"mx4gemm", run_mx4gemm, run_mx4gemm_check, 2048},
 };
@@ -370,8 +378,9 @@ int main(int argc, char** argv) {
     } else if (std::strcmp(cmd, "serve") == 0) {
       // warm-pool worker: one line per request, one JSON line per reply
       //   vecadd <n> | busy <ms> | gemm [M N K] | dgemm [M N K] |
-      //   mxgemm [M N K] | mx4gemm [M N K] | attn [B HQ HKV L] |
-      //   prefill [B HQ HKV L] | memcheck [BYTES] | ping | quit
+      //   igemm [M N K] | mxgemm [M N K] | mx4gemm [M N K] |
+      //   attn [B HQ HKV L] | prefill [B HQ HKV L] | memcheck [BYTES] |
+      //   ping | quit
       std::string line;
       while (std::getline(std::cin, line)) {
         std::istringstream iss(line);

@@ -24,6 +24,7 @@ using f32_array = c_array<float>;
 using f64_array = c_array<double>;
 using u32_array = c_array<uint32_t>;
 using u8_array = c_array<uint8_t>;
+using i8_array = c_array<int8_t>;
 
 // out[i] = f(x[i]): an array of x's shape, any rank
 template <class Out, class In>
@@ -158,6 +159,30 @@ py::array_t<float> gemm_raw(const char* who, GemmRawEntry entry,
   return c;
 }
 
+// an int8 operand of the INT8 GEMM entries as a contiguous array. Another
+// integer dtype is not cast: a value outside int8 would wrap silently, so it
+// is a TypeError
+i8_array int8_operand(const char* who, const char* what, const py::object& x) {
+  if (!py::isinstance<py::array>(x) ||
+      !py::reinterpret_borrow<py::array>(x).dtype().is(py::dtype::of<int8_t>()))
+    throw py::type_error(std::string(who) + ": " + what + " must be an int8 array");
+  return i8_array::ensure(x);
+}
+
+// (M, N, K) of the INT8 GEMM entries: gemm_dims plus the K limit
+std::array<int, 3> igemm_dims(const char* who, const i8_array& a, const i8_array& b) {
+  auto dims = gemm_dims(who, a, b);
+  if (dims[2] > payload::kIgemmMaxK)
+    throw py::value_error(std::string(who) + ": K must be <= 131071");
+  return dims;
+}
+
+// a W8A8 scale vector: `n` floats
+void scale_vector(const char* who, const char* what, const f32_array& s, int n) {
+  if (s.ndim() != 1 || s.shape(0) != n)
+    throw py::value_error(std::string(who) + ": " + what + " has the wrong length");
+}
+
 // the report of one of the timed GEMM runs
 using TimedGemm = payload::GemmResult (*)(int, int, int, int, int);
 py::dict run_timed_gemm(TimedGemm run, int mm, int n, int k, int iters, int device) {
@@ -247,7 +272,7 @@ py::dict attn_timed_dict(int batch, int hq, int hkv, int length, int iters) {
 
 PYBIND11_MODULE(_payload, m) {
   m.doc() = "gfx950 HIP payload kernels (vecadd / membw / busy / xcd census / gemm / "
-            "mxgemm / mx4gemm / memcheck / attn / prefill)";
+            "dgemm / igemm / mxgemm / mx4gemm / memcheck / attn / prefill)";
 
   m.def("device_count", &payload::device_count,
         "Number of visible HIP devices (0 if no GPU/driver)");
@@ -455,6 +480,97 @@ PYBIND11_MODULE(_payload, m) {
       py::arg("m") = 4096, py::arg("n") = 4096, py::arg("k") = 1024,
       py::arg("iters") = 10, py::arg("device") = 0,
       "timed FP64 MFMA GEMM, 256 outputs spot-checked exactly; K <= 65536");
+
+  // ---- INT8 -----------------------------------------------------------------
+
+  m.def(
+      "gemm_i8",
+      [](py::object a_, py::object b_, int device) {
+        const char* who = "gemm_i8";
+        i8_array a = int8_operand(who, "a", a_), b = int8_operand(who, "b", b_);
+        auto [M, N, K] = igemm_dims(who, a, b);
+        py::array_t<int32_t> c({static_cast<py::ssize_t>(M), static_cast<py::ssize_t>(N)});
+        const int8_t* pa = a.data();
+        const int8_t* pb = b.data();
+        int32_t* pc = c.mutable_data();
+        {
+          py::gil_scoped_release rel;
+          payload::gemm_i8(pa, pb, pc, M, N, K, device);
+        }
+        return c;
+      },
+      py::arg("a"), py::arg("b"), py::arg("device") = 0,
+      "C (M,N) int32 = a (M,K) @ b (K,N), int8 operands and int32 accumulation on "
+      "the INT8 MFMA kernel; TypeError unless both are int8 arrays, ValueError on "
+      "K > 131071 (beyond it an int32 sum could wrap)");
+
+  m.def(
+      "gemm_w8a8",
+      [](py::object a_, py::object b_, f32_array sa, f32_array sb, int device) {
+        const char* who = "gemm_w8a8";
+        i8_array a = int8_operand(who, "a", a_), b = int8_operand(who, "b", b_);
+        auto [M, N, K] = igemm_dims(who, a, b);
+        scale_vector(who, "sa", sa, M);
+        scale_vector(who, "sb", sb, N);
+        py::array_t<float> c({static_cast<py::ssize_t>(M), static_cast<py::ssize_t>(N)});
+        const int8_t* pa = a.data();
+        const int8_t* pb = b.data();
+        const float* psa = sa.data();
+        const float* psb = sb.data();
+        float* pc = c.mutable_data();
+        {
+          py::gil_scoped_release rel;
+          payload::gemm_w8a8(pa, pb, psa, psb, pc, M, N, K, device);
+        }
+        return c;
+      },
+      py::arg("a"), py::arg("b"), py::arg("sa"), py::arg("sb"), py::arg("device") = 0,
+      "C (M,N) float32 = (float32(a (M,K) @ b (K,N)) * sa[:, None]) * sb[None, :]: "
+      "the int32 product of int8 operands scaled per row (sa, M floats) and per "
+      "column (sb, N floats) in the kernel's epilogue, in fp32 and in that order; "
+      "TypeError unless a and b are int8 arrays, ValueError on K > 131071, a scale "
+      "vector of the wrong length or a non-finite scale");
+
+  m.def(
+      "quantize_i8",
+      [](f32_array x) {
+        const int K = last_axis("quantize_i8", "x", x);
+        std::vector<py::ssize_t> shape(x.shape(), x.shape() + x.ndim());
+        py::array_t<int8_t> codes(shape);
+        shape.pop_back();
+        py::array_t<float> scales(shape);
+        const float* src = x.data();
+        int8_t* pc = codes.mutable_data();
+        float* ps = scales.mutable_data();
+        for (py::ssize_t r = 0, rows = x.size() / K; r < rows; ++r)
+          payload::quantize_i8_row(src + r * K, K, pc + r * K, ps + r);
+        return py::make_tuple(codes, scales);
+      },
+      py::arg("x"),
+      "symmetric int8 quantization along the last axis: (codes int8 [..., K], "
+      "scales float32 [...]), scale = absmax / 127 (1 for an all-zero row), code = "
+      "round-to-nearest-even of x / scale in -127 .. 127; ValueError on a "
+      "non-finite element; host only, no GPU");
+
+  m.def(
+      "run_igemm_check",
+      [](int mm, int n, int k, int device) {
+        py::gil_scoped_release rel;
+        return payload::run_igemm_check(mm, n, k, device);
+      },
+      py::arg("m"), py::arg("n"), py::arg("k"), py::arg("device") = 0,
+      "INT8 GEMM (int32 result) on a pattern over the whole int8 range vs host "
+      "int64 reference; returns max abs error (expect 0); K <= 131071");
+
+  m.def(
+      "run_igemm",
+      [](int mm, int n, int k, int iters, int device) {
+        return run_timed_gemm(payload::run_igemm, mm, n, k, iters, device);
+      },
+      py::arg("m") = 4096, py::arg("n") = 4096, py::arg("k") = 4096,
+      py::arg("iters") = 10, py::arg("device") = 0,
+      "timed INT8 MFMA GEMM, 256 outputs spot-checked exactly; \"tflops\" is "
+      "10^12 integer operations per second (2 M N K per launch); K <= 131071");
 
   m.def(
       "to_e4m3",

@@ -57,6 +57,16 @@ answer, not a slightly different one. None of the other probes issues a
 double-precision instruction, so a partition can pass all of them and still
 fail here. Its TFLOP/s is carried in the report and never judged.
 
+So is the integer one. `run_igemm` runs `instaslice-payload igemm` (the INT8
+MFMA GEMM: int8 operands and int32 accumulation on `v_mfma_i32_32x32x32_i8`,
+exact-checked and timed at 4096 x 4096 x 4096 on a pattern that covers the
+whole int8 range, -128 included) and `judge_igemm` fails "igemm" unless the
+maximum error is exactly zero: an integer result is right or wrong, never
+close. It is the path a W8A8-quantised model runs on, an instruction family
+and accumulator layout none of the other probes issues. Its `tflops` field
+counts integer operations (2 M N K per launch, in units of 10**12 per second);
+it is carried in the report and never judged.
+
 So has the serving path. `run_attn` runs `instaslice-payload attn` (KV-cache
 decode attention: single-token grouped-query attention at head dim 128, K and
 V streamed through the bf16 MFMA with an fp32 online softmax and a split-KV
@@ -334,6 +344,30 @@ def run_dgemm(profile_name: str, env: Optional[Dict[str, str]] = None,
     parse_profile_name(profile_name)
     return _run_child(profile_name, ["dgemm"], CHILD_TIMEOUT_S, "max_err",
                       lambda report: judge_dgemm(report, profile_name),
+                      env, runner)
+
+
+# ---- igemm ------------------------------------------------------------------
+
+def judge_igemm(report: dict, profile_name: str) -> dict:
+    """Judge an `instaslice-payload igemm` report: "igemm" fails unless
+    `max_err` is a numeric zero and `m`, `n`, `k`, `iters` are integer counts
+    >= 1. `tflops` (integer operations) is carried and never judged. Pure; the
+    report's own `ok` is not trusted. ValueError on a profile name that does
+    not parse."""
+    return _judge_one(report, profile_name, "igemm", _mx_fields_clean)
+
+
+def run_igemm(profile_name: str, env: Optional[Dict[str, str]] = None,
+              runner: Callable = subprocess.run) -> dict:
+    """Run `instaslice-payload igemm` (default shape and iterations) in a
+    fresh child with `env` and judge its report, with the same contract as
+    `run_mxgemm`: every way the child can fail comes back as `ok: False`
+    with a `reason`, and only an unparseable profile name raises
+    (ValueError)."""
+    parse_profile_name(profile_name)
+    return _run_child(profile_name, ["igemm"], CHILD_TIMEOUT_S, "max_err",
+                      lambda report: judge_igemm(report, profile_name),
                       env, runner)
 
 
