@@ -19,7 +19,7 @@
     python -m instaslice_amd top        --store HOST:PORT [--interval S]
     python -m instaslice_amd cordon     --store HOST:PORT --node N [--uncordon]
     python -m instaslice_amd payload    [info|vecadd|membw|busy|census|gemm|
-                                         dgemm|igemm|mxgemm|mx4gemm|attn|
+                                         dgemm|igemm|mxgemm|mx4gemm|moe|attn|
                                          prefill|memcheck|verify] ...
     python -m instaslice_amd verify     --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
@@ -33,6 +33,8 @@
     python -m instaslice_amd dgemm      --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
     python -m instaslice_amd igemm      --profile NAME
+                                        [--visible-devices UUID_OR_INDEX]
+    python -m instaslice_amd moe        --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
     python -m instaslice_amd attn       --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
@@ -438,6 +440,13 @@ def cmd_igemm(args) -> int:
     return _probe(args, "run_igemm")
 
 
+def cmd_moe(args) -> int:
+    """Run the routed mixture-of-experts grouped GEMM payload inside the
+    visible partition and judge it against the requested profile; prints the
+    judged JSON, exit 0 iff ok."""
+    return _probe(args, "run_moe")
+
+
 def cmd_attn(args) -> int:
     """Run the KV-cache decode attention payload inside the visible partition
     and judge it against the requested profile; prints the judged JSON, exit
@@ -611,6 +620,16 @@ def main(argv=None) -> int:
                    help="ROCR_VISIBLE_DEVICES for the probe (partition UUID "
                         "or index); default: inherit the environment")
     p.set_defaults(fn=cmd_igemm)
+
+    p = sub.add_parser("moe",
+                       help="exact-check and time the routed mixture-of-experts "
+                            "path of the visible partition, judge it against a "
+                            "profile")
+    p.add_argument("--profile", required=True, help="e.g. cpx-1x36")
+    p.add_argument("--visible-devices", default=None,
+                   help="ROCR_VISIBLE_DEVICES for the probe (partition UUID "
+                        "or index); default: inherit the environment")
+    p.set_defaults(fn=cmd_moe)
 
     p = sub.add_parser("attn",
                        help="check and time KV-cache decode attention (the "

@@ -41,6 +41,16 @@
 //                the 4-bit matrix path, the same instruction with other format
 //                selectors and half the operand registers
 //                (payload_mxfp4.hpp, included below)
+//   moe          routed mixture-of-experts grouped GEMM: rows gathered through
+//                an index tensor, a ragged M extent per expert known only on
+//                the device, tiles scheduled from a table the routing kernels
+//                (LDS histograms, integer atomics, a one-workgroup scan) wrote
+//                a moment earlier, the bf16 MFMA in a 128-row and a 32-row
+//                geometry, results scaled by the gate, sent back through the
+//                permutation and reduced over a token's top-k experts in a
+//                fixed order; exact-checked and timed: the layer an MoE model
+//                keeps its weights and FLOPs in (payload_moe.hpp, included
+//                below)
 //   memcheck    moving-inversions memory test with an address-derived
 //                pattern at streaming rate: the HBM a profile promises is
 //                there, holds data and does not alias (payload_memcheck.hpp,
@@ -592,6 +602,10 @@ inline int device_count() {
 
 // INT8 MFMA GEMM payload: the bf16 one's LDS offset rule, GemmShape and drivers
 #include "payload_igemm.hpp"
+
+// routed mixture-of-experts grouped GEMM payload: the bf16 one's vector types,
+// LDS offset rule, bf16 rounding, pattern and require_exact_k
+#include "payload_moe.hpp"
 
 // MXFP8 block-scaled MFMA GEMM payload: same helpers, plus the gemm pattern
 #include "payload_mxgemm.hpp"

@@ -47,6 +47,17 @@
 //                                             mxgemm pattern (default 4096
 //                                             4096 2048, 10 iters; K <= 2048);
 //                                             exit 1 unless max_err == 0
+//   instaslice-payload moe [T N K E TOPK [ITERS]]
+//                                             routed mixture-of-experts grouped
+//                                             GEMM (routing on the device, a
+//                                             gathered bf16 MFMA GEMM per
+//                                             expert, gate, top-k combine),
+//                                             timed over the whole path, then
+//                                             256 outputs checked exactly
+//                                             (default 8192 4096 1024 32 4, 10
+//                                             iters; K <= 1024); "bm" is the
+//                                             tile height the host chose;
+//                                             exit 1 unless max_err == 0
 //   instaslice-payload memcheck [BYTES [PASSES [FLIP_OFFSET FLIP_MASK]]]
 //                                             moving-inversions memory test
 //                                             of one BYTES buffer (default
@@ -205,6 +216,35 @@ static void print_gemm_check(const GemmVerb& g, std::istringstream& iss) {
       err == 0.0 ? "true" : "false", g.name, m, n, k, json_num(err));
 }
 
+// moe [T N K E TOPK [ITERS]]: the timed run, with the host's choice of bm
+static bool print_timed_moe(int argc, char** argv) {
+  int a[5] = {8192, 4096, 1024, 32, 4};
+  if (argc > 6)
+    for (int i = 0; i < 5; ++i) a[i] = std::atoi(argv[2 + i]);
+  int iters = argc > 7 ? std::atoi(argv[7]) : 10;
+  MoeResult r = run_moe(a[0], a[1], a[2], a[3], a[4], iters);
+  bool ok = r.max_err == 0.0;
+  std::printf(
+      "{\"ok\": %s, \"cmd\": \"moe\", \"tokens\": %d, \"n\": %d, \"k\": %d, "
+      "\"experts\": %d, \"topk\": %d, \"bm\": %d, \"iters\": %d, \"tflops\": %.2f, "
+      "\"tokens_per_s\": %.1f, \"max_err\": %g}\n",
+      ok ? "true" : "false", a[0], a[1], a[2], a[3], a[4], r.bm, iters, r.tflops,
+      r.tokens_per_s, json_num(r.max_err));
+  return ok;
+}
+
+// serve's moe [T N K E TOPK]: the full check, the host's choice of bm. The
+// default has an empty expert (3) and two experts with two tiles each.
+static void print_moe_check(std::istringstream& iss) {
+  int a[5] = {300, 160, 224, 6, 2}, t[5];
+  if (iss >> t[0] >> t[1] >> t[2] >> t[3] >> t[4]) std::memcpy(a, t, sizeof(a));
+  double err = run_moe_check(a[0], a[1], a[2], a[3], a[4]);
+  std::printf(
+      "{\"ok\": %s, \"cmd\": \"moe\", \"tokens\": %d, \"n\": %d, \"k\": %d, "
+      "\"experts\": %d, \"topk\": %d, \"max_err\": %g}\n",
+      err == 0.0 ? "true" : "false", a[0], a[1], a[2], a[3], a[4], json_num(err));
+}
+
 // the two attention payloads share their verbs' shape arguments and the head
 // of their report lines; a verb starts from its defaults
 struct AttnArgs {
@@ -299,6 +339,8 @@ int main(int argc, char** argv) {
       std::printf("], \"xcds_visible\": %d}\n", census.xcds());
     } else if (const GemmVerb* g = find_gemm_verb(cmd)) {
       return print_timed_gemm(*g, argc, argv) ? 0 : 1;
+    } else if (std::strcmp(cmd, "moe") == 0) {
+      return print_timed_moe(argc, argv) ? 0 : 1;
     } else if (std::strcmp(cmd, "attn") == 0) {
       AttnArgs a{32, 64, 8, 4096};
       a.parse(argc, argv);
@@ -379,8 +421,8 @@ int main(int argc, char** argv) {
       // warm-pool worker: one line per request, one JSON line per reply
       //   vecadd <n> | busy <ms> | gemm [M N K] | dgemm [M N K] |
       //   igemm [M N K] | mxgemm [M N K] | mx4gemm [M N K] |
-      //   attn [B HQ HKV L] | prefill [B HQ HKV L] | memcheck [BYTES] |
-      //   ping | quit
+      //   moe [T N K E TOPK] | attn [B HQ HKV L] | prefill [B HQ HKV L] |
+      //   memcheck [BYTES] | ping | quit
       std::string line;
       while (std::getline(std::cin, line)) {
         std::istringstream iss(line);
@@ -397,6 +439,8 @@ int main(int argc, char** argv) {
             print_vecadd(n);
           } else if (const GemmVerb* g = find_gemm_verb(verb.c_str())) {
             print_gemm_check(*g, iss);
+          } else if (verb == "moe") {
+            print_moe_check(iss);
           } else if (verb == "attn") {
             AttnArgs a{2, 8, 2, 300};
             a.parse(iss);

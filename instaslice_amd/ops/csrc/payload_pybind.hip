@@ -183,6 +183,28 @@ void scale_vector(const char* who, const char* what, const f32_array& s, int n) 
     throw py::value_error(std::string(who) + ": " + what + " has the wrong length");
 }
 
+// the (T, topk) ids of the routed entries as ints. A floating array is a
+// TypeError, not a cast: a cast would hide a wrong value. An id beyond int is
+// passed on as -1, which the host layer refuses like any id outside [0, E)
+std::vector<int> moe_ids(const char* who, const py::object& ids_) {
+  std::string w(who);
+  if (!py::isinstance<py::array>(ids_))
+    throw py::type_error(w + ": ids must be an integer array");
+  const char kind = py::reinterpret_borrow<py::array>(ids_).dtype().kind();
+  if (kind != 'i' && kind != 'u')
+    throw py::type_error(w + ": ids must be an integer array");
+  auto ids = c_array<int64_t>::ensure(ids_);
+  if (!ids) throw py::type_error(w + ": ids must be an integer array");
+  if (ids.ndim() != 2 || ids.shape(0) < 1 || ids.shape(1) < 1 ||
+      ids.shape(0) > INT32_MAX || ids.shape(1) > payload::kMoeMaxTopk)
+    throw py::value_error(w + ": ids must be (T, topk), T >= 1 and 1 <= topk <= 8");
+  std::vector<int> out(ids.size());
+  const int64_t* src = ids.data();
+  for (size_t i = 0; i < out.size(); ++i)
+    out[i] = src[i] < 0 || src[i] > INT32_MAX ? -1 : static_cast<int>(src[i]);
+  return out;
+}
+
 // the report of one of the timed GEMM runs
 using TimedGemm = payload::GemmResult (*)(int, int, int, int, int);
 py::dict run_timed_gemm(TimedGemm run, int mm, int n, int k, int iters, int device) {
@@ -272,7 +294,7 @@ py::dict attn_timed_dict(int batch, int hq, int hkv, int length, int iters) {
 
 PYBIND11_MODULE(_payload, m) {
   m.doc() = "gfx950 HIP payload kernels (vecadd / membw / busy / xcd census / gemm / "
-            "dgemm / igemm / mxgemm / mx4gemm / memcheck / attn / prefill)";
+            "dgemm / igemm / mxgemm / mx4gemm / moe / memcheck / attn / prefill)";
 
   m.def("device_count", &payload::device_count,
         "Number of visible HIP devices (0 if no GPU/driver)");
@@ -571,6 +593,120 @@ PYBIND11_MODULE(_payload, m) {
       py::arg("iters") = 10, py::arg("device") = 0,
       "timed INT8 MFMA GEMM, 256 outputs spot-checked exactly; \"tflops\" is "
       "10^12 integer operations per second (2 M N K per launch); K <= 131071");
+
+  // ---- routed mixture of experts ---------------------------------------------
+
+  m.def(
+      "moe_gemm",
+      [](f32_array x, f32_array w, py::object ids_, py::object gates_, int bm,
+         int device) {
+        const std::string who = "moe_gemm";
+        if (x.ndim() != 2 || w.ndim() != 3)
+          throw py::value_error(who + ": x must be (T,K) and w (E,K,N)");
+        std::vector<int> ids = moe_ids("moe_gemm", ids_);
+        const py::array_t<int64_t> shape_of = c_array<int64_t>::ensure(ids_);
+        const py::ssize_t T = x.shape(0), K = x.shape(1), topk = shape_of.shape(1);
+        if (shape_of.shape(0) != T)
+          throw py::value_error(who + ": x is (T,K) and ids is (T,topk): T differs");
+        if (w.shape(1) != K)
+          throw py::value_error(who + ": x is (T,K) and w is (E,K,N): K differs");
+        if (K < 1 || w.shape(0) < 1 || w.shape(2) < 1)
+          throw py::value_error(who + ": empty operand");
+        if (K > INT32_MAX || w.shape(0) > INT32_MAX || w.shape(2) > INT32_MAX)
+          throw py::value_error(who + ": shape too large");
+        f32_array gates;
+        if (!gates_.is_none()) {
+          gates = f32_array::ensure(gates_);
+          if (!gates) throw py::type_error(who + ": gates must be a float array or None");
+          if (gates.ndim() != 2 || gates.shape(0) != T || gates.shape(1) != topk)
+            throw py::value_error(who + ": gates must be (T, topk) like ids");
+        }
+        const int E = static_cast<int>(w.shape(0)), N = static_cast<int>(w.shape(2));
+        py::array_t<float> y({T, static_cast<py::ssize_t>(N)});
+        const float* px = x.data();
+        const float* pw = w.data();
+        const float* pg = gates_.is_none() ? nullptr : gates.data();
+        float* py_ = y.mutable_data();
+        {
+          py::gil_scoped_release rel;
+          payload::moe_gemm(px, pw, ids.data(), pg, py_, static_cast<int>(T), N,
+                            static_cast<int>(K), E, static_cast<int>(topk), bm, device);
+        }
+        return y;
+      },
+      py::arg("x"), py::arg("w"), py::arg("ids"), py::arg("gates") = py::none(),
+      py::arg("bm") = 0, py::arg("device") = 0,
+      "y (T,N) float32: y[t] = sum_j gates[t,j] * (bf16(x[t]) @ bf16(w[ids[t,j]])), "
+      "the routed mixture-of-experts layer on the grouped MFMA GEMM: x (T,K), w "
+      "(E,K,N), ids (T,topk) integer with a token's experts all different, gates "
+      "(T,topk) or None (all ones); routing on the device, fp32 accumulation, the "
+      "gate applied in fp32, the top-k rows added in the order of j; bm 0 (the "
+      "host's choice), 32 or 128 picks the tile height; TypeError on floating ids, "
+      "ValueError on a bad shape, E > 256, topk > min(E, 8), an id outside [0, E), "
+      "a repeated expert, a non-finite element or another bm");
+
+  m.def(
+      "moe_route",
+      [](py::object ids_, int experts, int device) {
+        std::vector<int> ids = moe_ids("moe_route", ids_);
+        const py::array_t<int64_t> shape_of = c_array<int64_t>::ensure(ids_);
+        const int T = static_cast<int>(shape_of.shape(0));
+        const int topk = static_cast<int>(shape_of.shape(1));
+        if (experts < 1 || experts > payload::kMoeMaxExperts)
+          throw py::value_error("moe_route: experts must be in 1 .. 256");
+        py::array_t<int32_t> perm(static_cast<py::ssize_t>(ids.size()));
+        py::array_t<int32_t> seg(static_cast<py::ssize_t>(experts) + 1);
+        int* pp = perm.mutable_data();
+        int* ps = seg.mutable_data();
+        {
+          py::gil_scoped_release rel;
+          payload::moe_route(ids.data(), T, topk, experts, pp, ps, device);
+        }
+        return py::make_tuple(perm, seg);
+      },
+      py::arg("ids"), py::arg("experts"), py::arg("device") = 0,
+      "the routing kernels alone on ids (T,topk): (perm int32 (T*topk,), the slot "
+      "t*topk+j at each row of the expert-sorted order, seg int32 (experts+1,), "
+      "the start of each expert's run); the order inside a run is not fixed");
+
+  m.def(
+      "run_moe_check",
+      [](int tokens, int n, int k, int experts, int topk, int bm, int device) {
+        py::gil_scoped_release rel;
+        return payload::run_moe_check(tokens, n, k, experts, topk, bm, device);
+      },
+      py::arg("tokens"), py::arg("n"), py::arg("k"), py::arg("experts"),
+      py::arg("topk"), py::arg("bm") = 0, py::arg("device") = 0,
+      "routed grouped GEMM on an integer pattern with an empty expert vs host "
+      "int64 reference; returns max abs error (expect 0); K <= 1024");
+
+  m.def(
+      "run_moe",
+      [](int tokens, int n, int k, int experts, int topk, int iters, int bm,
+         int device) {
+        payload::MoeResult r;
+        {
+          py::gil_scoped_release rel;
+          r = payload::run_moe(tokens, n, k, experts, topk, iters, bm, device);
+        }
+        py::dict d;
+        d["tokens"] = tokens;
+        d["n"] = n;
+        d["k"] = k;
+        d["experts"] = experts;
+        d["topk"] = topk;
+        d["bm"] = r.bm;
+        d["iters"] = iters;
+        d["tflops"] = r.tflops;
+        d["tokens_per_s"] = r.tokens_per_s;
+        d["max_err"] = r.max_err;
+        return d;
+      },
+      py::arg("tokens") = 8192, py::arg("n") = 4096, py::arg("k") = 1024,
+      py::arg("experts") = 32, py::arg("topk") = 4, py::arg("iters") = 10,
+      py::arg("bm") = 0, py::arg("device") = 0,
+      "timed routed grouped GEMM (route, GEMM and combine per launch), 256 outputs "
+      "spot-checked exactly; tflops counts 2 T topk N K per launch; K <= 1024");
 
   m.def(
       "to_e4m3",

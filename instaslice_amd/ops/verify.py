@@ -67,6 +67,16 @@ and accumulator layout none of the other probes issues. Its `tflops` field
 counts integer operations (2 M N K per launch, in units of 10**12 per second);
 it is carried in the report and never judged.
 
+So has the routed path. `run_moe` runs `instaslice-payload moe` (the
+mixture-of-experts grouped GEMM: routing on the device with LDS histograms and
+integer atomics, a gathered bf16 MFMA GEMM per expert scheduled from the tile
+table the routing wrote, the gate, and the combine over a token's top-k
+experts, exact-checked and timed at 8192 tokens x 4096 x 1024 over 32 experts,
+top-4) and `judge_moe` fails "moe" unless the maximum error is exactly zero
+and `bm`, the tile height the host chose, is 32 or 128. None of the dense
+probes takes an index, so a partition can pass all of them and be wrong here.
+Its rates are carried in the report and never judged.
+
 So has the serving path. `run_attn` runs `instaslice-payload attn` (KV-cache
 decode attention: single-token grouped-query attention at head dim 128, K and
 V streamed through the bf16 MFMA with an fp32 online softmax and a split-KV
@@ -368,6 +378,36 @@ def run_igemm(profile_name: str, env: Optional[Dict[str, str]] = None,
     parse_profile_name(profile_name)
     return _run_child(profile_name, ["igemm"], CHILD_TIMEOUT_S, "max_err",
                       lambda report: judge_igemm(report, profile_name),
+                      env, runner)
+
+
+# ---- moe --------------------------------------------------------------------
+
+def _moe_fields_clean(report: dict) -> bool:
+    return _is_zero(report.get("max_err")) \
+        and _counts_from_one(report, ("tokens", "n", "k", "experts", "topk",
+                                      "iters")) \
+        and _is_count(report.get("bm")) and report["bm"] in (32, 128)
+
+
+def judge_moe(report: dict, profile_name: str) -> dict:
+    """Judge an `instaslice-payload moe` report: "moe" fails unless `max_err`
+    is a numeric zero, `tokens`, `n`, `k`, `experts`, `topk`, `iters` are
+    integer counts >= 1 and `bm` is 32 or 128. `tflops` and `tokens_per_s` are
+    carried and never judged. Pure; the report's own `ok` is not trusted.
+    ValueError on a profile name that does not parse."""
+    return _judge_one(report, profile_name, "moe", _moe_fields_clean)
+
+
+def run_moe(profile_name: str, env: Optional[Dict[str, str]] = None,
+            runner: Callable = subprocess.run) -> dict:
+    """Run `instaslice-payload moe` (default shape and iterations) in a fresh
+    child with `env` and judge its report, with the same contract as
+    `run_igemm`: every way the child can fail comes back as `ok: False` with
+    a `reason`, and only an unparseable profile name raises (ValueError)."""
+    parse_profile_name(profile_name)
+    return _run_child(profile_name, ["moe"], CHILD_TIMEOUT_S, "max_err",
+                      lambda report: judge_moe(report, profile_name),
                       env, runner)
 
 
