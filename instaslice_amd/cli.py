@@ -20,7 +20,7 @@
     python -m instaslice_amd cordon     --store HOST:PORT --node N [--uncordon]
     python -m instaslice_amd payload    [info|vecadd|membw|busy|census|gemm|
                                          dgemm|igemm|mxgemm|mx4gemm|moe|attn|
-                                         prefill|memcheck|verify] ...
+                                         paged|prefill|memcheck|verify] ...
     python -m instaslice_amd verify     --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
     python -m instaslice_amd memcheck   --profile NAME [--gb G | --fraction F]
@@ -37,6 +37,8 @@
     python -m instaslice_amd moe        --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
     python -m instaslice_amd attn       --profile NAME
+                                        [--visible-devices UUID_OR_INDEX]
+    python -m instaslice_amd paged      --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
     python -m instaslice_amd prefill   --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
@@ -454,6 +456,13 @@ def cmd_attn(args) -> int:
     return _probe(args, "run_attn")
 
 
+def cmd_paged(args) -> int:
+    """Run the paged, ragged-batch decode attention payload inside the visible
+    partition and judge it against the requested profile; prints the judged
+    JSON, exit 0 iff ok."""
+    return _probe(args, "run_paged")
+
+
 def cmd_prefill(args) -> int:
     """Run the causal prefill attention payload inside the visible partition
     and judge it against the requested profile; prints the judged JSON, exit
@@ -640,6 +649,17 @@ def main(argv=None) -> int:
                    help="ROCR_VISIBLE_DEVICES for the probe (partition UUID "
                         "or index); default: inherit the environment")
     p.set_defaults(fn=cmd_attn)
+
+    p = sub.add_parser("paged",
+                       help="check and time decode attention over a paged KV "
+                            "cache (block table, ragged lengths, work planned "
+                            "on the device) in the visible partition, judge it "
+                            "against a profile")
+    p.add_argument("--profile", required=True, help="e.g. cpx-1x36")
+    p.add_argument("--visible-devices", default=None,
+                   help="ROCR_VISIBLE_DEVICES for the probe (partition UUID "
+                        "or index); default: inherit the environment")
+    p.set_defaults(fn=cmd_paged)
 
     p = sub.add_parser("prefill",
                        help="check and time causal prefill attention (the "

@@ -1,0 +1,761 @@
+// gfx950 paged, ragged-batch KV-cache decode attention payload.
+//
+// attn (payload_attn.hpp) streams a cache that the host lays out as one
+// contiguous, equally padded run of chunk images per (sequence, kv head), with
+// one split count for the whole batch. An inference server keeps a pool of
+// fixed-size pages instead, reaches a sequence's pages through a block table,
+// batches lengths that differ by orders of magnitude and lets sequences share
+// the pages of a common prefix. This payload is that path:
+//
+//   o[b,h,:] = softmax_t(scale * q[b,h,:] . K_b[g,t,:]) . V_b[g,t,:],  t < len[b]
+//
+// where key t of sequence b lives in physical page table[b][t / page], at key
+// t % page of it. The arithmetic (QK, key order, base-2 online softmax with the
+// -inf guards, P in registers, PV, the merge weights) is the contiguous
+// kernel's; what is new is how a chunk is found and how the work is split.
+//
+//   cache        a pool of P pages of `page` keys, page in {32, 64, 128, 256}.
+//                Page p holds, for each kv head g and each 32-key chunk c of
+//                the page, one K image and one V image of 4096 bf16 in the
+//                fragment order of attn_k_off / attn_v_off, at image index
+//                (p * Hkv + g) * (page / 32) + c.
+//   table        int32 [B][W]. Only the entries below ceil(len[b] / page) are
+//                read; they lie in 0 .. P - 1 (the host checks). The others
+//                may hold anything. A page may appear in several sequences.
+//   stale keys   keys at and beyond len[b] inside a chunk that is read are
+//                masked by index: K there may be any finite value, V must be
+//                finite (its weight is an exact 0 that goes through the MFMA).
+//                Chunks at and beyond ceil(len[b] / 32) are never read, nor
+//                are pages that no entry below a length names.
+//   plan         lengths change every decode step, so the split is computed on
+//                the device, in every launch. attn_paged_plan_kernel (one
+//                workgroup) sums the batch's chunks C, takes a budget per =
+//                ceil(C / target) chunks per item and gives sequence b n_b =
+//                ceil(chunks_b / per) items of near-equal chunk ranges: an LDS
+//                prefix scan over b, 256 sequences per stride with a carry.
+//                It writes the item table {b, chunk_begin, chunk_end, item of
+//                the sequence} and per sequence {first part, n_b * 4}. Items
+//                never span sequences, so there are at most target + B of
+//                them; the order is that of (b, chunk), so results do not
+//                depend on timing. attn_paged_plan() is the same arithmetic on
+//                the host and the specification.
+//   decode       grid (Hkv, target + B), 4 wave64s, no LDS, no barrier; a
+//                workgroup beyond the item count leaves at once, and those are
+//                the last of the grid. The item's chunks are dealt round-robin
+//                to the waves. A wave resolves a chunk by a wave-uniform
+//                scalar load of its table entry and forms the image address in
+//                size_t. K is requested one chunk ahead, so the table entry is
+//                fetched two chunks ahead: the indirection's latency sits
+//                under the previous chunk's MFMAs and softmax, not in front of
+//                the K loads. Every wave writes one unnormalised (m, l,
+//                o[128]); a wave with no chunk writes m = -inf.
+//   combine      one workgroup per output row merges the row's n_b * 4
+//                partials, a count that differs per sequence.
+//
+// Partials of row (b, h) start at first_part[b] * Hq + h * n_b * 4, part =
+// item of the sequence * 4 + wave: a row's partials are contiguous.
+//
+// Included by payload_core.hpp after payload_attn.hpp, whose helpers it uses:
+// the layout and pattern functions, attn_p_bf16, detail::attn_ref_row, the
+// dense hash pattern and kAttnRelBound.
+
+#pragma once
+
+#include <numeric>
+
+namespace payload {
+
+constexpr int kAttnPagedMaxTarget = 4096;  // `workgroups` at most
+
+// ---- the plan --------------------------------------------------------------
+
+struct AttnPagedPlan {
+  std::vector<int> items;  // 3 per item: b, chunk_begin, chunk_end
+  std::vector<int> seq;    // 2 per sequence: first part, parts (items * 4)
+};
+
+__host__ __device__ inline int attn_paged_chunks(int len) {
+  return (len + kAttnChunk - 1) / kAttnChunk;
+}
+
+// chunk where item j of n starts in a sequence of c chunks (j = n: c)
+__host__ __device__ inline int attn_paged_cut(int c, int n, int j) {
+  return static_cast<int>(static_cast<long long>(c) * j / n);
+}
+
+// The specification of attn_paged_plan_kernel. lens[b] >= 1, target in 1 ..
+// 4096, sum_b ceil(lens[b] / 32) below 2^31.
+inline AttnPagedPlan attn_paged_plan(const int* lens, int B, int target) {
+  if (B < 1 || target < 1 || target > kAttnPagedMaxTarget)
+    throw std::invalid_argument("attn_paged_plan: B >= 1 and target in 1 .. 4096");
+  long long C = 0;
+  for (int b = 0; b < B; ++b) {
+    if (lens[b] < 1) throw std::invalid_argument("attn_paged_plan: lengths must be >= 1");
+    C += attn_paged_chunks(lens[b]);
+  }
+  if (C > INT32_MAX) throw std::invalid_argument("attn_paged_plan: too many chunks");
+  const int per = static_cast<int>((C + target - 1) / target);
+  AttnPagedPlan p;
+  int first = 0;
+  for (int b = 0; b < B; ++b) {
+    const int c = attn_paged_chunks(lens[b]), n = (c + per - 1) / per;
+    p.seq.push_back(first * kAttnWaves);
+    p.seq.push_back(n * kAttnWaves);
+    for (int j = 0; j < n; ++j) {
+      p.items.push_back(b);
+      p.items.push_back(attn_paged_cut(c, n, j));
+      p.items.push_back(attn_paged_cut(c, n, j + 1));
+    }
+    first += n;
+  }
+  return p;
+}
+
+// ---- kernels -------------------------------------------------------------
+
+// One workgroup. lens: [B], clamped to 0 .. Lmax. items: target + B entries.
+// seq: [B]. nitems: one int.
+__global__ __launch_bounds__(kBlock) void attn_paged_plan_kernel(
+    const int* __restrict__ lens, int B, int Lmax, int target,
+    int4* __restrict__ items, int2* __restrict__ seq, int* __restrict__ nitems) {
+  __shared__ int scan[kBlock];
+  __shared__ int carry;
+  const int tid = threadIdx.x;
+
+  int mine = 0;  // chunks of the sequences tid, tid + 256, ...
+  for (int b = tid; b < B; b += kBlock)
+    mine += attn_paged_chunks(min(max(lens[b], 0), Lmax));
+  scan[tid] = mine;
+  if (tid == 0) carry = 0;
+  __syncthreads();
+  int top = 1;  // entries at and beyond min(B, 256) are zero
+  while (top < min(B, kBlock)) top <<= 1;
+  for (int d = top / 2; d > 0; d >>= 1) {
+    if (tid < d) scan[tid] += scan[tid + d];
+    __syncthreads();
+  }
+  const int C = scan[0];
+  const int per = max(1, (C + target - 1) / target);
+  __syncthreads();
+
+  for (int b0 = 0; b0 < B; b0 += kBlock) {  // block-uniform
+    const int b = b0 + tid;
+    const int c = b < B ? attn_paged_chunks(min(max(lens[b], 0), Lmax)) : 0;
+    const int n = (c + per - 1) / per;
+    scan[tid] = n;
+    __syncthreads();
+    const int live = min(kBlock, B - b0);  // the rest of scan is zero
+    for (int d = 1; d < live; d <<= 1) {  // inclusive scan of the live entries
+      const int v = tid >= d ? scan[tid - d] : 0;
+      __syncthreads();
+      scan[tid] += v;
+      __syncthreads();
+    }
+    const int first = carry + scan[tid] - n;
+    if (b < B) seq[b] = make_int2(first * kAttnWaves, n * kAttnWaves);
+    for (int j = 0; j < n; ++j)
+      items[first + j] =
+          make_int4(b, attn_paged_cut(c, n, j), attn_paged_cut(c, n, j + 1), j);
+    __syncthreads();  // every thread has read carry
+    if (tid == live - 1) carry += scan[tid];
+    __syncthreads();
+  }
+  if (tid == 0) *nitems = carry;
+}
+
+// q: [B][Hkv][16][128] bf16, rows G .. 15 zero. kp, vp: the pool's chunk
+// images. table: [B][W]. shift = log2(page / 32). Partials as described at the
+// top. grid = (Hkv, target + B): the kv head is the fast index, so that the
+// workgroups beyond the item count are the last to be dispatched and take no
+// CU from a live one. The chunk step is attn_decode_kernel's.
+__global__ __launch_bounds__(kBlock) void attn_paged_decode_kernel(
+    const uint16_t* __restrict__ q, const uint16_t* __restrict__ kp,
+    const uint16_t* __restrict__ vp, const int* __restrict__ table,
+    const int* __restrict__ lens, const int4* __restrict__ items,
+    const int* __restrict__ nitems, const int2* __restrict__ seq,
+    float* __restrict__ pm, float* __restrict__ pl, float* __restrict__ po, int G,
+    int W, int shift, int Lmax, float c2) {
+  if (static_cast<int>(blockIdx.y) >= *nitems) return;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int fr = lane & 15, fq = lane >> 4;
+  const int g = blockIdx.x, Hkv = gridDim.x;
+
+  const int4 it = items[blockIdx.y];
+  const int b = it.x, ch_end = it.z;
+  const int len = min(max(lens[b], 0), Lmax);
+  const int* trow = table + static_cast<size_t>(b) * W;
+  const int cmask = (1 << shift) - 1;
+
+  // element offset of this lane's first fragment in chunk ch of physical page pg
+  auto image = [&](int pg, int ch) {
+    const size_t idx =
+        ((static_cast<size_t>(pg) * Hkv + g) << shift) + static_cast<size_t>(ch & cmask);
+    return idx * kAttnChunkElems + static_cast<size_t>(lane) * 8;
+  };
+
+  bf16x8 fqt[kAttnD / 32];
+  {
+    const uint16_t* qb =
+        q + ((static_cast<size_t>(b) * Hkv + g) * 16 + fr) * kAttnD + fq * 8;
+#pragma unroll
+    for (int s = 0; s < kAttnD / 32; ++s)
+      fqt[s] = *reinterpret_cast<const bf16x8*>(qb + s * 32);
+  }
+
+  float m = -INFINITY, l = 0.f;
+  f32x4 o[kAttnD / 16];
+#pragma unroll
+  for (int dt = 0; dt < kAttnD / 16; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  bf16x8 fk[2][kAttnD / 32];
+  auto load_k = [&](int pg, int ch) {
+    const uint16_t* kc = kp + image(pg, ch);
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int s = 0; s < kAttnD / 32; ++s)
+        fk[t][s] = *reinterpret_cast<const bf16x8*>(kc + (t * 4 + s) * 512);
+  };
+
+  // pg_v: the page of the chunk in hand (its K is in flight or here); pg_k: the
+  // page of the wave's next chunk, fetched a whole chunk before its K loads
+  int ch = it.y + wave;
+  int pg_v = 0, pg_k = 0;
+  if (ch < ch_end) {
+    pg_v = trow[ch >> shift];
+    load_k(pg_v, ch);
+  }
+  if (ch + kAttnWaves < ch_end) pg_k = trow[(ch + kAttnWaves) >> shift];
+
+  for (; ch < ch_end; ch += kAttnWaves) {  // wave-uniform
+    const int c0 = ch * kAttnChunk;
+    const uint16_t* vc = vp + image(pg_v, ch);
+    bf16x8 fv[kAttnD / 16];
+#pragma unroll
+    for (int dt = 0; dt < kAttnD / 16; ++dt)
+      fv[dt] = *reinterpret_cast<const bf16x8*>(vc + dt * 512);
+
+    f32x4 st[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int s = 0; s < kAttnD / 32; ++s)
+        st[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fk[t][s], fqt[s], st[t],
+                                                        0, 0, 0);
+
+    const int nx = ch + kAttnWaves;
+    if (nx < ch_end) load_k(pg_k, nx);
+    pg_v = pg_k;
+    if (nx + kAttnWaves < ch_end) pg_k = trow[(nx + kAttnWaves) >> shift];
+
+    float sc[8];
+    float cm = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int key = c0 + 8 * fq + j;
+      sc[j] = key < len ? st[j >> 2][j & 3] * c2 : -INFINITY;
+      cm = fmaxf(cm, sc[j]);
+    }
+    cm = fmaxf(cm, __shfl_xor(cm, 16));
+    cm = fmaxf(cm, __shfl_xor(cm, 32));
+
+    const float mn = fmaxf(m, cm);
+    const float ms = mn == -INFINITY ? 0.f : mn;  // never (-inf) - (-inf)
+    const float alpha = __builtin_amdgcn_exp2f(m - ms);  // m = -inf: 0
+    m = mn;
+
+    bf16x8 fp;
+    float sum = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float p = __builtin_amdgcn_exp2f(sc[j] - ms);
+      sum += p;  // l takes the unrounded weight
+      fp[j] = attn_p_bf16(p);
+    }
+    l = l * alpha + sum;
+
+#pragma unroll
+    for (int dt = 0; dt < kAttnD / 16; ++dt) {
+      o[dt] *= alpha;
+      o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fv[dt], fp, o[dt], 0, 0, 0);
+    }
+  }
+
+  l += __shfl_xor(l, 16);
+  l += __shfl_xor(l, 32);
+
+  if (fr < G) {
+    const int2 sq = seq[b];
+    const size_t Hq = static_cast<size_t>(Hkv) * G;
+    const size_t part = static_cast<size_t>(sq.x) * Hq +
+                        (static_cast<size_t>(g) * G + fr) * sq.y +
+                        static_cast<size_t>(it.w) * kAttnWaves + wave;
+    if (fq == 0) {
+      pm[part] = m;
+      pl[part] = l;
+    }
+#pragma unroll
+    for (int dt = 0; dt < kAttnD / 16; ++dt)
+      *reinterpret_cast<f32x4*>(po + part * kAttnD + dt * 16 + fq * 4) = o[dt];
+  }
+}
+
+// attn_combine_kernel over a row's own part count. grid = B Hq, block = 128.
+__global__ __launch_bounds__(kAttnD) void attn_paged_combine_kernel(
+    const float* __restrict__ pm, const float* __restrict__ pl,
+    const float* __restrict__ po, const int2* __restrict__ seq,
+    float* __restrict__ out, int Hq) {
+  const size_t row = blockIdx.x;
+  const int d = threadIdx.x;
+  const int2 sq = seq[row / Hq];
+  const int P = sq.y;
+  const size_t base = static_cast<size_t>(sq.x) * Hq + (row % Hq) * P;
+  const float* m = pm + base;
+  const float* l = pl + base;
+  const float* o = po + base * kAttnD + d;
+  float mx = -INFINITY;
+  for (int i = 0; i < P; ++i) mx = fmaxf(mx, m[i]);
+  float ls = 0.f, acc = 0.f;
+  for (int i = 0; i < P; ++i) {
+    const float mi = m[i];
+    if (mi == -INFINITY) continue;  // a wave with no chunk: weight 0
+    const float w = __builtin_amdgcn_exp2f(mi - mx);
+    ls += w * l[i];
+    acc += w * o[static_cast<size_t>(i) * kAttnD];
+  }
+  out[row * kAttnD + d] = acc / ls;  // the only division, and a true one
+}
+
+// Device-side fill of the selection pattern at the lengths lens[b], one
+// fragment of each tensor per thread and step, over the logical chunks of all
+// W pages of every sequence; keys at and beyond lens[b] are zero. The image of
+// logical chunk lc of (b, g) is found through the table, or, with table null,
+// at (b * Hkv + g) * chunks + lc: the contiguous layout of payload_attn.hpp.
+__global__ __launch_bounds__(kBlock) void attn_paged_fill_kernel(
+    uint16_t* __restrict__ k, uint16_t* __restrict__ vt, const int* __restrict__ table,
+    const int* __restrict__ lens, int Hkv, int W, int shift,
+    size_t groups) {  // groups = B Hkv (W << shift) 4096 / 8, per tensor
+  size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
+  const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  const size_t chunks = static_cast<size_t>(W) << shift;
+  for (; i < groups; i += stride) {
+    const size_t image = i / 512, bg = image / chunks;
+    const int lc = static_cast<int>(image % chunks), c0 = lc * kAttnChunk;
+    const int b = static_cast<int>(bg / Hkv), g = static_cast<int>(bg % Hkv);
+    const int L = lens[b];
+    size_t dst = image;
+    if (table) {
+      const size_t pg = static_cast<size_t>(table[static_cast<size_t>(b) * W + (lc >> shift)]);
+      dst = ((pg * Hkv + g) << shift) + (lc & ((1 << shift) - 1));
+    }
+    const int frag = static_cast<int>(i / 64) & 7, lane = static_cast<int>(i) & 63;
+    const int fr = lane & 15, fq = lane >> 4;
+    bf16x8 kv, vv;
+    {
+      const int t = c0 + 8 * (fr >> 2) + 4 * (frag >> 2) + (fr & 3);
+      const int d0 = 32 * (frag & 3) + 8 * fq;
+      const bool sel = t < L && attn_selected(b, g, t, L);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        int val = 0;
+        if (t < L && !sel) val = attn_pat_k_off(g, t, d0 + j);
+        kv[j] = static_cast<short>(attn_int_bf16(val));
+      }
+    }
+    {
+      const int d = 16 * frag + fr;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int t = c0 + 8 * fq + j;
+        vv[j] = static_cast<short>(attn_int_bf16(t < L ? attn_pat_v(b, g, t, d) : 0));
+      }
+    }
+    const size_t at = (dst * 512 + i % 512) * 8;
+    *reinterpret_cast<bf16x8*>(k + at) = kv;
+    *reinterpret_cast<bf16x8*>(vt + at) = vv;
+  }
+}
+
+// ---- host layer ----------------------------------------------------------
+
+struct AttnPagedResult : AttnResult {
+  int items = 0;  // of the last launch
+};
+
+// The limits of the paged payload, or std::invalid_argument; no HIP call.
+// Returns Hq / Hkv.
+inline int attn_paged_shape(long long B, long long Hq, long long Hkv, long long page,
+                            long long W, long long P, long long workgroups = 0) {
+  const long long G = detail::attn_group("attn_paged", B, Hq, Hkv, 1);
+  if (G > kAttnMaxGroup)
+    throw std::invalid_argument("attn_paged: Hq / Hkv must be <= 16");
+  if (page != 32 && page != 64 && page != 128 && page != 256)
+    throw std::invalid_argument("attn_paged: page must be 32, 64, 128 or 256");
+  if (W < 1 || P < 1)
+    throw std::invalid_argument("attn_paged: W and P must be >= 1");
+  if (workgroups < 0 || workgroups > kAttnPagedMaxTarget)
+    throw std::invalid_argument("attn_paged: workgroups must be in 0 .. 4096");
+  if (B > 65535 - kAttnPagedMaxTarget || Hkv > 65535 || P > INT32_MAX || W > (1 << 28) / page ||
+      B * W * (page / kAttnChunk) > INT32_MAX)
+    throw std::invalid_argument("attn_paged: shape too large");
+  return static_cast<int>(G);
+}
+
+namespace detail {
+
+// Lengths in 1 .. W page, and every table entry that will be read in 0 .. P - 1
+inline void attn_paged_check_table(const int* table, const int* lens, int B, int page,
+                                   int W, int P) {
+  for (int b = 0; b < B; ++b) {
+    if (lens[b] < 1 || lens[b] > static_cast<long long>(W) * page)
+      throw std::invalid_argument("attn_paged: lengths must be in 1 .. W * page");
+    const int used = (lens[b] + page - 1) / page;
+    for (int w = 0; w < used; ++w) {
+      const int pg = table[static_cast<size_t>(b) * W + w];
+      if (pg < 0 || pg >= P)
+        throw std::invalid_argument(
+            "attn_paged: a table entry below a length is outside 0 .. P - 1");
+    }
+  }
+}
+
+// a table of B W different pages out of P >= B W, scrambled: entry i names
+// page (i a + 1) % P with a coprime to P
+inline std::vector<int> attn_paged_scrambled_table(int B, int W, int P) {
+  long long a = 7919;
+  while (std::gcd(a, static_cast<long long>(P)) != 1) a += 2;
+  std::vector<int> table(static_cast<size_t>(B) * W);
+  for (size_t i = 0; i < table.size(); ++i)
+    table[i] = static_cast<int>((static_cast<long long>(i) * a + 1) % P);
+  return table;
+}
+
+// Shape, device buffers and launch of one paged problem.
+struct AttnPagedProblem : AttnShape {
+  int page, W, P, shift, target;
+  DeviceBuffer dq, dk, dvt, dtable, dlens, ditems, dseq, dnitems, dpm, dpl, dpo, dout;
+
+  // L is the longest a sequence may be, W page; the shape is checked before
+  // that product is formed
+  AttnPagedProblem(int b, int hq, int hkv, int pg, int w, int p, int workgroups, int dev)
+      : AttnShape{b, hq, hkv, 0, attn_paged_shape(b, hq, hkv, pg, w, p, workgroups), dev},
+        page(pg), W(w), P(p), shift(pg == 32 ? 0 : pg == 64 ? 1 : pg == 128 ? 2 : 3),
+        target(workgroups) {
+    L = w * pg;
+  }
+
+  size_t pool_elems() const {
+    return static_cast<size_t>(P) * Hkv * page * kAttnD;
+  }
+  size_t rows() const { return static_cast<size_t>(B) * Hq; }
+  int max_items() const { return target + B; }
+
+  // workgroups = 0: items for half the visible CUs, the count that
+  // profiles/attn_probe.md found best for the contiguous kernel
+  void alloc() {
+    HIP_CHECK(hipSetDevice(device));
+    if (target == 0) {
+      int cus = 0;
+      HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
+                                      device));
+      target = std::max(1, cus / (2 * Hkv));
+    }
+    const size_t parts = static_cast<size_t>(max_items()) * kAttnWaves * Hq;
+    dq.alloc(static_cast<size_t>(B) * Hkv * 16 * kAttnD * sizeof(uint16_t));
+    dk.alloc(pool_elems() * sizeof(uint16_t));
+    dvt.alloc(pool_elems() * sizeof(uint16_t));
+    dtable.alloc(static_cast<size_t>(B) * W * sizeof(int));
+    dlens.alloc(static_cast<size_t>(B) * sizeof(int));
+    ditems.alloc(static_cast<size_t>(max_items()) * sizeof(int4));
+    dseq.alloc(static_cast<size_t>(B) * sizeof(int2));
+    dnitems.alloc(sizeof(int));
+    dpm.alloc(parts * sizeof(float));
+    dpl.alloc(parts * sizeof(float));
+    dpo.alloc(parts * kAttnD * sizeof(float));
+    dout.alloc(rows() * kAttnD * sizeof(float));
+  }
+
+  // q (B, Hq, 128) float -> the padded bf16 image; the table and the lengths
+  void upload_q_table(const float* q, const int* table, const int* lens) {
+    std::vector<uint16_t> hq(static_cast<size_t>(B) * Hkv * 16 * kAttnD, 0);
+    for (int b = 0; b < B; ++b)
+      for (int h = 0; h < Hq; ++h) {
+        const size_t dst = ((static_cast<size_t>(b) * Hkv + h / G) * 16 + h % G) * kAttnD;
+        const float* src = q + (static_cast<size_t>(b) * Hq + h) * kAttnD;
+        for (int d = 0; d < kAttnD; ++d) hq[dst + d] = to_bf16_rne(src[d]);
+      }
+    HIP_CHECK(hipMemcpy(dq.p, hq.data(), hq.size() * sizeof(uint16_t),
+                        hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dtable.p, table, static_cast<size_t>(B) * W * sizeof(int),
+                        hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dlens.p, lens, static_cast<size_t>(B) * sizeof(int),
+                        hipMemcpyHostToDevice));
+  }
+
+  // k_pages, v_pages (P, Hkv, page, 128) float -> the pool's chunk images, every
+  // page of it, referenced or not
+  void upload_pool(const float* k, const float* v) {
+    std::vector<uint16_t> hk(pool_elems()), hvt(pool_elems());
+    const size_t heads = static_cast<size_t>(P) * Hkv;
+    for (size_t pgh = 0; pgh < heads; ++pgh)
+      for (int t = 0; t < page; ++t) {
+        const size_t src = (pgh * page + t) * kAttnD;
+        const size_t image = ((pgh << shift) + t / kAttnChunk) * kAttnChunkElems;
+        const int w = t % kAttnChunk;
+        for (int d = 0; d < kAttnD; ++d) {
+          hk[image + attn_k_off(w, d)] = to_bf16_rne(k[src + d]);
+          hvt[image + attn_v_off(w, d)] = to_bf16_rne(v[src + d]);
+        }
+      }
+    HIP_CHECK(hipMemcpy(dk.p, hk.data(), hk.size() * sizeof(uint16_t),
+                        hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dvt.p, hvt.data(), hvt.size() * sizeof(uint16_t),
+                        hipMemcpyHostToDevice));
+  }
+
+  // plan + decode + combine
+  void launch(float scale) const {
+    hipLaunchKernelGGL(attn_paged_plan_kernel, dim3(1), dim3(kBlock), 0, 0,
+                       dlens.as<const int>(), B, L, target, ditems.as<int4>(),
+                       dseq.as<int2>(), dnitems.as<int>());
+    dim3 grid(static_cast<unsigned>(Hkv), static_cast<unsigned>(max_items()));
+    hipLaunchKernelGGL(attn_paged_decode_kernel, grid, dim3(kBlock), 0, 0,
+                       dq.as<const uint16_t>(), dk.as<const uint16_t>(),
+                       dvt.as<const uint16_t>(), dtable.as<const int>(),
+                       dlens.as<const int>(), ditems.as<const int4>(),
+                       dnitems.as<const int>(), dseq.as<const int2>(), dpm.as<float>(),
+                       dpl.as<float>(), dpo.as<float>(), G, W, shift, L, attn_c2(scale));
+    hipLaunchKernelGGL(attn_paged_combine_kernel, dim3(static_cast<unsigned>(rows())),
+                       dim3(kAttnD), 0, 0, dpm.as<const float>(), dpl.as<const float>(),
+                       dpo.as<const float>(), dseq.as<const int2>(), dout.as<float>(),
+                       Hq);
+  }
+
+  int items() const {
+    int n = 0;
+    HIP_CHECK(hipMemcpy(&n, dnitems.p, sizeof(int), hipMemcpyDeviceToHost));
+    return n;
+  }
+};
+
+// the fixed ragged rule of the timed run: L for every eighth sequence, L / 8
+// for the rest
+inline std::vector<int> attn_paged_lens(int B, int L, bool ragged) {
+  std::vector<int> lens(B, L);
+  if (ragged)
+    for (int b = 0; b < B; ++b)
+      if (b % 8 != 0) lens[b] = std::max(1, L / 8);
+  return lens;
+}
+
+// dense (B, Hkv, L, 128), L >= lens[b] -> the pool (P, Hkv, page, 128) under
+// the table: the keys below lens[b], and `stale` at the further keys of the
+// last chunk that is read. Nothing else of the pool is written.
+inline void attn_paged_scatter(const float* dense, float* pool, const int* table,
+                               const int* lens, int B, int Hkv, int L, int page, int W,
+                               float stale) {
+  for (int b = 0; b < B; ++b) {
+    const int read = static_cast<int>(round_up(lens[b], kAttnChunk));
+    for (int g = 0; g < Hkv; ++g)
+      for (int t = 0; t < read; ++t) {
+        const size_t pg = static_cast<size_t>(table[static_cast<size_t>(b) * W + t / page]);
+        float* dst = pool + ((pg * Hkv + g) * page + t % page) * kAttnD;
+        const float* src =
+            dense + ((static_cast<size_t>(b) * Hkv + g) * L + std::min(t, L - 1)) * kAttnD;
+        for (int d = 0; d < kAttnD; ++d) dst[d] = t < lens[b] ? src[d] : stale;
+      }
+  }
+}
+
+}  // namespace detail
+
+// General entry. q (B, Hq, 128), k_pages and v_pages (P, Hkv, page, 128), o (B,
+// Hq, 128), all row-major float; table (B, W) and lens (B) int32; workgroups 0
+// = auto. std::invalid_argument on an unsupported shape, a length outside 1 ..
+// W page, a table entry below a length outside 0 .. P - 1, or a non-finite q or
+// key of a chunk that will be read; all before any device work.
+inline void attn_paged_decode(const float* q, const float* k_pages, const float* v_pages,
+                              const int* table, const int* lens, float* o, int B, int Hq,
+                              int Hkv, int page, int W, int P, float scale,
+                              int workgroups = 0, int device = 0) {
+  detail::AttnPagedProblem p(B, Hq, Hkv, page, W, P, workgroups, device);
+  detail::attn_paged_check_table(table, lens, B, page, W, P);
+  for (size_t i = 0, n = p.rows() * kAttnD; i < n; ++i)
+    if (!std::isfinite(q[i]))
+      throw std::invalid_argument("attn_paged: q has a non-finite element");
+  for (int b = 0; b < B; ++b) {
+    const int read = static_cast<int>(detail::round_up(lens[b], kAttnChunk));
+    for (int g = 0; g < Hkv; ++g)
+      for (int t = 0; t < read; ++t) {
+        const size_t pg = static_cast<size_t>(table[static_cast<size_t>(b) * W + t / page]);
+        const size_t at = ((pg * Hkv + g) * page + t % page) * kAttnD;
+        for (int d = 0; d < kAttnD; ++d)
+          if (!std::isfinite(k_pages[at + d]) || !std::isfinite(v_pages[at + d]))
+            throw std::invalid_argument(
+                "attn_paged: k or v has a non-finite element in a chunk that is read");
+      }
+  }
+  p.alloc();
+  p.upload_q_table(q, table, lens);
+  p.upload_pool(k_pages, v_pages);
+  p.launch(scale);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemcpy(o, p.dout.p, p.rows() * kAttnD * sizeof(float),
+                      hipMemcpyDeviceToHost));
+}
+
+// Self-check on ragged lengths derived from L, sequence b taking entry b % 4 of
+// {L, 1, the largest multiple of 32 up to max(32, L / 2), max(1, L / page) page
+// + 1}: from B = 4 on the batch holds a single key, a whole number of chunks
+// and one key past a page boundary. The pool has B more pages than the table
+// names, all NaN; the table is scrambled and holds -1 above a sequence's
+// length; stale keys of a read chunk hold 1e30 in K and V. (a) the selection
+// pattern against its closed form: max_err, expect exactly 0. (b) the dense
+// hash pattern of run_attn_check against fp64: max_rel <= 2^-8, the bound
+// derived there, which does not depend on how the keys are split.
+inline AttnCheck run_attn_paged_check(int B, int Hq, int Hkv, int L, int page,
+                                      int workgroups = 0, int device = 0) {
+  if (L < 1 || L > (1 << 24))
+    throw std::invalid_argument("attn_paged: L must be in 1 .. 2^24");
+  attn_paged_shape(B, Hq, Hkv, page, 1, 1, workgroups);  // page before it divides
+  const int rule[4] = {L, 1, std::max(32, L / 2) / 32 * 32, std::max(1, L / page) * page + 1};
+  const int Lmax = *std::max_element(rule, rule + 4);
+  const int W = (Lmax + page - 1) / page;
+  const long long Pll = static_cast<long long>(B) * W + B;
+  const int G = attn_paged_shape(B, Hq, Hkv, page, W, Pll, workgroups);
+  const int P = static_cast<int>(Pll);
+  std::vector<int> lens(B);
+  for (int b = 0; b < B; ++b) lens[b] = rule[b % 4];
+  std::vector<int> table = detail::attn_paged_scrambled_table(B, W, P);
+  for (int b = 0; b < B; ++b)
+    for (int w = (lens[b] + page - 1) / page; w < W; ++w)
+      table[static_cast<size_t>(b) * W + w] = -1;
+
+  const size_t nq = static_cast<size_t>(B) * Hq * kAttnD;
+  const size_t nkv = static_cast<size_t>(B) * Hkv * Lmax * kAttnD;
+  const size_t npool = static_cast<size_t>(P) * Hkv * page * kAttnD;
+  const float scale = detail::attn_default_scale();
+  std::vector<float> q(nq), k(nkv), v(nkv), want(nq), got(nq);
+  std::vector<float> kpool(npool, NAN), vpool(npool, NAN);
+  AttnCheck r;
+  auto decode = [&] {
+    detail::attn_paged_scatter(k.data(), kpool.data(), table.data(), lens.data(), B, Hkv,
+                               Lmax, page, W, 1e30f);
+    detail::attn_paged_scatter(v.data(), vpool.data(), table.data(), lens.data(), B, Hkv,
+                               Lmax, page, W, 1e30f);
+    attn_paged_decode(q.data(), kpool.data(), vpool.data(), table.data(), lens.data(),
+                      got.data(), B, Hq, Hkv, page, W, P, scale, workgroups, device);
+  };
+
+  attn_check_pattern(q.data(), k.data(), v.data(), want.data(), B, Hq, Hkv, Lmax,
+                     lens.data());
+  decode();
+  for (size_t i = 0; i < nq; ++i)
+    detail::note_err(r.max_err, std::fabs(static_cast<double>(got[i]) -
+                                          static_cast<double>(want[i])));
+
+  double vmax = 0;
+  for (size_t i = 0; i < nq; ++i) q[i] = detail::attn_dense(1, i, 256);
+  for (size_t i = 0; i < nkv; ++i) {
+    k[i] = detail::attn_dense(2, i, 64);
+    v[i] = detail::attn_dense(3, i, 64);
+    vmax = std::max(vmax, std::fabs(static_cast<double>(v[i])));
+  }
+  decode();
+  std::vector<double> w(Lmax), ref(kAttnD);
+  double max_abs = 0;
+  for (int b = 0; b < B; ++b)
+    for (int h = 0; h < Hq; ++h) {
+      const size_t bg = static_cast<size_t>(b) * Hkv + h / G;
+      const size_t at = (static_cast<size_t>(b) * Hq + h) * kAttnD;
+      detail::attn_ref_row(ref.data(), q.data() + at, k.data() + bg * Lmax * kAttnD,
+                           v.data() + bg * Lmax * kAttnD, lens[b],
+                           static_cast<double>(scale), w);
+      for (int d = 0; d < kAttnD; ++d)
+        detail::note_err(max_abs, std::fabs(static_cast<double>(got[at + d]) - ref[d]));
+    }
+  r.max_rel = vmax > 0 ? max_abs / vmax : max_abs;
+  return r;
+}
+
+// Timed run on the selection pattern: W = ceil(L / page) pages per sequence
+// under a fixed scrambled table over a pool of B W + 3 pages, filled on the
+// device through the table; one warm-up launch, `iters` launches (plan + decode
+// + combine) between events, then 16 spread (b, h) rows are checked exactly.
+// KV bytes are sum_b lens[b] Hkv 128 2 2 per launch. `ragged` takes the lengths
+// of detail::attn_paged_lens. `contiguous` (L a multiple of `page`) times the
+// contiguous kernel of payload_attn.hpp on the same lengths and data instead,
+// for comparison: its cache is filled by the same kernel without a table.
+inline AttnPagedResult run_attn_paged(int B = 32, int Hq = 64, int Hkv = 8, int L = 4096,
+                                      int page = 64, int iters = 10, bool ragged = false,
+                                      int workgroups = 0, int device = 0,
+                                      bool contiguous = false) {
+  if (iters < 1) throw std::invalid_argument("run_attn_paged: iters must be >= 1");
+  if (L < 1 || L > (1 << 28))
+    throw std::invalid_argument("run_attn_paged: L must be in 1 .. 2^28");
+  attn_paged_shape(B, Hq, Hkv, page, 1, 1, workgroups);
+  const int W = (L + page - 1) / page;
+  const long long Pll = static_cast<long long>(B) * W + 3;
+  attn_paged_shape(B, Hq, Hkv, page, W, Pll, workgroups);
+  const int P = static_cast<int>(Pll);
+  const std::vector<int> lens = detail::attn_paged_lens(B, L, ragged);
+  const float scale = detail::attn_default_scale();
+  std::vector<float> q(static_cast<size_t>(B) * Hq * kAttnD);
+  detail::attn_pattern_q(q.data(), B, Hq);
+  double keys = 0;
+  for (int len : lens) keys += len;
+
+  AttnPagedResult r;
+  const size_t groups = static_cast<size_t>(B) * Hkv * W * page * kAttnD / 8;
+  // the rates of `iters` launches in ms, and the 16 rows of the output at dout
+  auto report = [&](float ms, const float* dout) {
+    const double sec = ms * 1e-3;
+    r.steps_per_s = iters / sec;
+    r.tok_per_s = r.steps_per_s * B;
+    r.kv_gb_s = keys * Hkv * kAttnD * 2.0 * 2.0 * iters / sec / 1e9;
+    std::vector<float> got(kAttnD), want(kAttnD);
+    const size_t rows = static_cast<size_t>(B) * Hq;
+    for (int t = 0; t < 16; ++t) {
+      const size_t row = detail::attn_spread_row(t, rows);
+      HIP_CHECK(hipMemcpy(got.data(), dout + row * kAttnD, kAttnD * sizeof(float),
+                          hipMemcpyDeviceToHost));
+      const int b = static_cast<int>(row / Hq);
+      detail::attn_pattern_row(want.data(), b, static_cast<int>(row % Hq), Hq / Hkv,
+                               lens[b]);
+      for (int d = 0; d < kAttnD; ++d)
+        detail::note_err(r.max_err, std::fabs(static_cast<double>(got[d]) -
+                                              static_cast<double>(want[d])));
+    }
+  };
+  if (contiguous) {
+    if (L % page != 0)
+      throw std::invalid_argument("run_attn_paged: contiguous needs L % page == 0");
+    detail::AttnProblem c(B, Hq, Hkv, L, 0, device);
+    c.alloc();
+    c.upload_q_lens(q.data(), lens.data());
+    hipLaunchKernelGGL(attn_paged_fill_kernel, dim3(grid_for(groups)), dim3(kBlock), 0, 0,
+                       c.dk.as<uint16_t>(), c.dvt.as<uint16_t>(),
+                       static_cast<const int*>(nullptr), c.dlens.as<const int>(), Hkv, W,
+                       __builtin_ctz(page / kAttnChunk), groups);
+    HIP_CHECK(hipGetLastError());
+    report(detail::time_launches(iters, [&c, scale] { c.launch(scale); }),
+           c.dout.as<float>());
+    r.items = B * c.splits;
+    return r;
+  }
+  detail::AttnPagedProblem p(B, Hq, Hkv, page, W, P, workgroups, device);
+  const std::vector<int> table = detail::attn_paged_scrambled_table(B, W, P);
+  p.alloc();
+  p.upload_q_table(q.data(), table.data(), lens.data());
+  hipLaunchKernelGGL(attn_paged_fill_kernel, dim3(grid_for(groups)), dim3(kBlock), 0, 0,
+                     p.dk.as<uint16_t>(), p.dvt.as<uint16_t>(), p.dtable.as<const int>(),
+                     p.dlens.as<const int>(), Hkv, W, p.shift, groups);
+  HIP_CHECK(hipGetLastError());
+  report(detail::time_launches(iters, [&p, scale] { p.launch(scale); }),
+         p.dout.as<float>());
+  r.items = p.items();
+  return r;
+}
+
+}  // namespace payload

@@ -60,7 +60,15 @@
 //                straight through the bf16 MFMA with an fp32 online softmax,
 //                exact-checked, bound-checked and timed: the hot kernel of an
 //                LLM server in decode (payload_attn.hpp, included below)
-//   prefill      causal prefill attention over a whole prompt (grouped-query,
+//   paged        the same attention over a paged cache and a ragged batch: a
+//                pool of fixed-size pages reached through a block table by
+//                wave-uniform scalar loads fetched two chunks ahead, lengths
+//                that differ within the batch, and a split into near-equal
+//                work items that a one-workgroup plan kernel (an LDS prefix
+//                scan) writes in every launch; exact-checked, bound-checked
+//                and timed: how a serving stack really keeps its cache
+//                (payload_attn_paged.hpp, included below)
+//   prefill     causal prefill attention over a whole prompt (grouped-query,
 //                head dim 128): K and V tiles staged through swizzled,
 //                double-buffered LDS and shared by the workgroup's waves, both
 //                products on the bf16 MFMA with the fp32 online softmax in
@@ -622,6 +630,10 @@ inline int device_count() {
 // shape limits (detail::AttnShape), the fp64 reference row, the check result
 // and its bound
 #include "payload_attn.hpp"
+
+// paged decode attention payload: the decode one's layout, patterns, chunk
+// arithmetic, reference row and bound
+#include "payload_attn_paged.hpp"
 
 // prefill attention payload: the decode one's head dim, patterns, scale and
 // shared host pieces

@@ -82,6 +82,22 @@
 //                                             the KV split count of the timed
 //                                             run; exit 1 unless max_err == 0
 //                                             and max_rel <= 2^-8
+//   instaslice-payload paged [B HQ HKV L [PAGE [ITERS [WORKGROUPS]]]]
+//                                             the same attention over a paged
+//                                             cache (a pool of PAGE-key pages
+//                                             behind a block table, PAGE 32,
+//                                             64, 128 or 256) with the split
+//                                             planned on the device: the
+//                                             self-check at 4 8 2 300, page 64,
+//                                             on ragged lengths, then a timed
+//                                             run (default 32 64 8 4096, page
+//                                             64, 10 iters; plan, decode and
+//                                             combine per launch) with 16 rows
+//                                             checked exactly; "items" is the
+//                                             plan's item count, WORKGROUPS (0
+//                                             or absent: auto) the count it
+//                                             aims at; exit 1 unless max_err
+//                                             == 0 and max_rel <= 2^-8
 //   instaslice-payload prefill [B HQ HKV L [ITERS [CAUSAL [PATTERN]]]]
 //                                             causal prefill attention (bf16
 //                                             MFMA, K and V tiles through LDS,
@@ -357,6 +373,25 @@ int main(int argc, char** argv) {
           iters, r.kv_gb_s, r.steps_per_s, r.tok_per_s, json_num(max_err),
           json_num(c.max_rel));
       return ok ? 0 : 1;
+    } else if (std::strcmp(cmd, "paged") == 0) {
+      AttnArgs a{32, 64, 8, 4096};
+      a.parse(argc, argv);
+      int page = argc > 6 ? std::atoi(argv[6]) : 64;
+      int iters = argc > 7 ? std::atoi(argv[7]) : 10;
+      int workgroups = argc > 8 ? std::atoi(argv[8]) : 0;
+      AttnCheck c = run_attn_paged_check(4, 8, 2, 300, 64);
+      AttnPagedResult r =
+          run_attn_paged(a.b, a.hq, a.hkv, a.len, page, iters, false, workgroups);
+      double max_err = r.max_err > c.max_err ? r.max_err : c.max_err;
+      bool ok = max_err == 0.0 && c.max_rel <= kAttnRelBound;
+      a.print_head("paged", ok);
+      std::printf(
+          "\"page\": %d, \"iters\": %d, \"items\": %d, \"kv_gb_per_s\": %.1f, "
+          "\"steps_per_s\": %.1f, \"tok_per_s\": %.1f, \"max_err\": %g, "
+          "\"max_rel\": %g}\n",
+          page, iters, r.items, r.kv_gb_s, r.steps_per_s, r.tok_per_s, json_num(max_err),
+          json_num(c.max_rel));
+      return ok ? 0 : 1;
     } else if (std::strcmp(cmd, "prefill") == 0) {
       AttnArgs a{8, 64, 8, 4096};
       a.parse(argc, argv);
@@ -421,8 +456,8 @@ int main(int argc, char** argv) {
       // warm-pool worker: one line per request, one JSON line per reply
       //   vecadd <n> | busy <ms> | gemm [M N K] | dgemm [M N K] |
       //   igemm [M N K] | mxgemm [M N K] | mx4gemm [M N K] |
-      //   moe [T N K E TOPK] | attn [B HQ HKV L] | prefill [B HQ HKV L] |
-      //   memcheck [BYTES] | ping | quit
+      //   moe [T N K E TOPK] | attn [B HQ HKV L] | paged [B HQ HKV L [PAGE]] |
+      //   prefill [B HQ HKV L] | memcheck [BYTES] | ping | quit
       std::string line;
       while (std::getline(std::cin, line)) {
         std::istringstream iss(line);
@@ -445,6 +480,15 @@ int main(int argc, char** argv) {
             AttnArgs a{2, 8, 2, 300};
             a.parse(iss);
             print_attn_check("attn", a, run_attn_check(a.b, a.hq, a.hkv, a.len), "");
+          } else if (verb == "paged") {
+            AttnArgs a{4, 8, 2, 300};
+            a.parse(iss);
+            int page = 64, tp;
+            if (iss >> tp) page = tp;
+            char extra[32];
+            std::snprintf(extra, sizeof(extra), "\"page\": %d, ", page);
+            print_attn_check("paged", a,
+                             run_attn_paged_check(a.b, a.hq, a.hkv, a.len, page), extra);
           } else if (verb == "prefill") {
             AttnArgs a{1, 4, 2, 200};
             a.parse(iss);

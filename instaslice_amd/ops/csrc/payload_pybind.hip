@@ -205,6 +205,33 @@ std::vector<int> moe_ids(const char* who, const py::object& ids_) {
   return out;
 }
 
+// an integer argument of the paged attention entries (the table, the lengths)
+// as int64 of rank `rank`. Anything floating is a TypeError, not a cast.
+c_array<int64_t> paged_ints(const char* who, const char* what, const py::object& x,
+                            int rank) {
+  const std::string w = std::string(who) + ": " + what;
+  py::array any = py::array::ensure(x);
+  if (!any) {
+    PyErr_Clear();
+    throw py::type_error(w + " must be an integer array");
+  }
+  const char kind = any.dtype().kind();
+  if (kind != 'i' && kind != 'u') throw py::type_error(w + " must be an integer array");
+  auto arr = c_array<int64_t>::ensure(any);
+  if (!arr) throw py::type_error(w + " must be an integer array");
+  if (arr.ndim() != rank) throw py::value_error(w + " has the wrong rank");
+  return arr;
+}
+
+// narrowed to int; what does not fit becomes -1, which no check admits
+std::vector<int> paged_narrow(const c_array<int64_t>& x) {
+  std::vector<int> out(static_cast<size_t>(x.size()));
+  const int64_t* src = x.data();
+  for (size_t i = 0; i < out.size(); ++i)
+    out[i] = src[i] < 0 || src[i] > INT32_MAX ? -1 : static_cast<int>(src[i]);
+  return out;
+}
+
 // the report of one of the timed GEMM runs
 using TimedGemm = payload::GemmResult (*)(int, int, int, int, int);
 py::dict run_timed_gemm(TimedGemm run, int mm, int n, int k, int iters, int device) {
@@ -294,7 +321,7 @@ py::dict attn_timed_dict(int batch, int hq, int hkv, int length, int iters) {
 
 PYBIND11_MODULE(_payload, m) {
   m.doc() = "gfx950 HIP payload kernels (vecadd / membw / busy / xcd census / gemm / "
-            "dgemm / igemm / mxgemm / mx4gemm / moe / memcheck / attn / prefill)";
+            "dgemm / igemm / mxgemm / mx4gemm / moe / memcheck / attn / paged / prefill)";
 
   m.def("device_count", &payload::device_count,
         "Number of visible HIP devices (0 if no GPU/driver)");
@@ -1044,6 +1071,141 @@ PYBIND11_MODULE(_payload, m) {
       py::arg("length") = 4096, py::arg("iters") = 10, py::arg("device") = 0,
       "timed decode attention on the selection pattern (device-filled cache, "
       "512 MiB of K and V at the default shape), 16 output rows checked exactly");
+
+  // ---- paged decode attention ------------------------------------------------
+
+  m.def(
+      "attn_paged_decode",
+      [](f32_array q, f32_array k_pages, f32_array v_pages, py::object table_,
+         py::object lens_, py::object scale, int workgroups, int device) {
+        const char* who = "attn_paged_decode";
+        const std::string w(who);
+        auto table = paged_ints(who, "table", table_, 2);
+        auto lens_arr = paged_ints(who, "lens", lens_, 1);
+        if (q.ndim() != 3) throw py::value_error(w + ": q must be (B,Hq,128)");
+        if (k_pages.ndim() != 4 || v_pages.ndim() != 4)
+          throw py::value_error(w + ": k_pages and v_pages must be (P,Hkv,page,128)");
+        if (q.shape(2) != payload::kAttnD || k_pages.shape(3) != payload::kAttnD)
+          throw py::value_error(w + ": head dim must be 128");
+        for (int i = 0; i < 4; ++i)
+          if (k_pages.shape(i) != v_pages.shape(i))
+            throw py::value_error(w + ": k_pages and v_pages differ in shape");
+        const py::ssize_t B = q.shape(0), Hq = q.shape(1), P = k_pages.shape(0),
+                          Hkv = k_pages.shape(1), page = k_pages.shape(2),
+                          W = table.shape(1);
+        if (table.shape(0) != B || lens_arr.shape(0) != B)
+          throw py::value_error(w + ": table must be (B,W) and lens (B,)");
+        payload::attn_paged_shape(B, Hq, Hkv, page, W, P, workgroups);
+        const std::vector<int> tab = paged_narrow(table), lens = paged_narrow(lens_arr);
+        const float sc = attn_scale(who, scale);
+        const float* pq = q.data();
+        const float* pk = k_pages.data();
+        const float* pv = v_pages.data();
+        py::array_t<float> o({B, Hq, static_cast<py::ssize_t>(payload::kAttnD)});
+        float* po = o.mutable_data();
+        {
+          py::gil_scoped_release rel;
+          payload::attn_paged_decode(pq, pk, pv, tab.data(), lens.data(), po,
+                                     static_cast<int>(B), static_cast<int>(Hq),
+                                     static_cast<int>(Hkv), static_cast<int>(page),
+                                     static_cast<int>(W), static_cast<int>(P), sc,
+                                     workgroups, device);
+        }
+        return o;
+      },
+      py::arg("q"), py::arg("k_pages"), py::arg("v_pages"), py::arg("table"),
+      py::arg("lens"), py::arg("scale") = py::none(), py::arg("workgroups") = 0,
+      py::arg("device") = 0,
+      "o (B,Hq,128) float32: single-token grouped-query attention over a paged KV "
+      "cache. q (B,Hq,128); k_pages and v_pages (P,Hkv,page,128), page 32, 64, 128 "
+      "or 256, rounded to bf16; table (B,W) integer names the physical page of each "
+      "logical page of a sequence, lens (B,) integer in 1 .. W*page. Only table "
+      "entries below ceil(lens[b]/page) are read and must be in 0 .. P-1; only the "
+      "chunks below ceil(lens[b]/32) are read and must be finite; a page may serve "
+      "several sequences. The split into work items is planned on the device from "
+      "lens; workgroups (0 = auto, at most 4096) is the item count it aims at; "
+      "scale=None is 1/sqrt(128). TypeError on a floating table or lens, ValueError "
+      "on an unsupported shape, length, table entry or a non-finite input, all "
+      "before any device work");
+
+  m.def(
+      "attn_paged_plan",
+      [](py::object lens_, int target) {
+        auto arr = paged_ints("attn_paged_plan", "lens", lens_, 1);
+        if (arr.shape(0) < 1 || arr.shape(0) > 65535)
+          throw py::value_error("attn_paged_plan: lens must hold 1 .. 65535 lengths");
+        const std::vector<int> lens = paged_narrow(arr);
+        const payload::AttnPagedPlan plan =
+            payload::attn_paged_plan(lens.data(), static_cast<int>(lens.size()), target);
+        py::array_t<int32_t> items({static_cast<py::ssize_t>(plan.items.size() / 3),
+                                    py::ssize_t{3}});
+        py::array_t<int32_t> seq({static_cast<py::ssize_t>(lens.size()), py::ssize_t{2}});
+        std::copy(plan.items.begin(), plan.items.end(), items.mutable_data());
+        std::copy(plan.seq.begin(), plan.seq.end(), seq.mutable_data());
+        return py::make_tuple(items, seq);
+      },
+      py::arg("lens"), py::arg("target"),
+      "the work plan of the paged decode kernel, computed on the host with the "
+      "arithmetic of the device's plan kernel: (items int32 (n,3) of (sequence, "
+      "chunk_begin, chunk_end) over 32-key chunks, seq int32 (B,2) of (first "
+      "partial, partials) per sequence); n <= target + B, target in 1 .. 4096; "
+      "host only, no GPU");
+
+  m.def(
+      "run_attn_paged_check",
+      [](int batch, int hq, int hkv, int length, int page, int workgroups, int device) {
+        payload::attn_paged_shape(batch, hq, hkv, page, 1, 1, workgroups);
+        if (length < 1 || length > (1 << 24))
+          throw py::value_error("run_attn_paged_check: length must be in 1 .. 2^24");
+        payload::AttnCheck r;
+        {
+          py::gil_scoped_release rel;
+          r = payload::run_attn_paged_check(batch, hq, hkv, length, page, workgroups,
+                                            device);
+        }
+        return attn_check_dict(r);
+      },
+      py::arg("batch"), py::arg("hq"), py::arg("hkv"), py::arg("length"),
+      py::arg("page") = 64, py::arg("workgroups") = 0, py::arg("device") = 0,
+      "paged decode attention self-check on ragged lengths derived from `length` "
+      "(the length itself, 1, a multiple of 32, a multiple of page plus one) under "
+      "a scrambled table with NaN in the unreferenced pages: max_err of the "
+      "selection pattern (expect exactly 0) and max_rel = max |o - fp64 ref| / max "
+      "|v| of a dense pattern (expect <= 2^-8)");
+
+  m.def(
+      "run_attn_paged",
+      [](int batch, int hq, int hkv, int length, int page, int iters, bool ragged,
+         int workgroups, int device, bool contiguous) {
+        payload::attn_paged_shape(batch, hq, hkv, page, 1, 1, workgroups);
+        if (iters < 1) throw py::value_error("run_attn_paged: iters must be >= 1");
+        payload::AttnPagedResult r;
+        {
+          py::gil_scoped_release rel;
+          r = payload::run_attn_paged(batch, hq, hkv, length, page, iters, ragged,
+                                      workgroups, device, contiguous);
+        }
+        py::dict d = attn_timed_dict(batch, hq, hkv, length, iters);
+        d["page"] = page;
+        d["ragged"] = ragged;
+        d["items"] = r.items;
+        d["kv_gb_per_s"] = r.kv_gb_s;
+        d["steps_per_s"] = r.steps_per_s;
+        d["tok_per_s"] = r.tok_per_s;
+        d["max_err"] = r.max_err;
+        return d;
+      },
+      py::arg("batch") = 32, py::arg("hq") = 64, py::arg("hkv") = 8,
+      py::arg("length") = 4096, py::arg("page") = 64, py::arg("iters") = 10,
+      py::arg("ragged") = false, py::arg("workgroups") = 0, py::arg("device") = 0,
+      py::arg("contiguous") = false,
+      "timed paged decode attention on the selection pattern (pool filled on the "
+      "device through a fixed scrambled table; plan, decode and combine per "
+      "launch), 16 output rows checked exactly; ragged=True gives every eighth "
+      "sequence `length` keys and the rest length/8; kv_gb_per_s counts the keys "
+      "below the lengths; items is the plan's item count; contiguous=True times "
+      "the contiguous kernel on the same lengths and data instead (length a "
+      "multiple of page), for comparison");
 
   // ---- prefill attention -----------------------------------------------------
 

@@ -85,6 +85,18 @@ merge; a self-check, then a timed run over 512 MiB of K and V) and
 the dense pattern's error relative to max |v| is within 2**-8, the bound that
 rounding the softmax weights to bf16 allows twice over. KV bytes/s, decode
 steps/s and tokens/s are carried in the report and never judged.
+
+So has the cache a serving stack really keeps. `run_paged` runs
+`instaslice-payload paged` (the same attention over a pool of fixed-size pages
+reached through a block table by scalar loads, with lengths that differ within
+the batch and a split into work items that a plan kernel writes on the device
+in every launch; a ragged self-check under a scrambled table, then a timed run
+over 512 MiB of K and V in 64-key pages) and `judge_paged` fails "paged" unless
+the exact pattern's maximum error is zero, the dense pattern's error is within
+the same 2**-8, the counts (`items` among them) are integers >= 1 and `page`
+is 32, 64, 128 or 256. `attn` addresses a chunk as base + chunk * 8 KiB, so a
+partition whose scalar-load-then-vector-load path is wrong passes it and fails
+here. Rates are carried in the report and never judged.
 """
 
 from __future__ import annotations
@@ -452,6 +464,37 @@ def run_attn(profile_name: str, env: Optional[Dict[str, str]] = None,
     parse_profile_name(profile_name)
     return _run_child(profile_name, ["attn"], CHILD_TIMEOUT_S, "max_err",
                       lambda report: judge_attn(report, profile_name),
+                      env, runner)
+
+
+# ---- paged ------------------------------------------------------------------
+
+PAGED_PAGES = (32, 64, 128, 256)
+
+
+def judge_paged(report: dict, profile_name: str) -> dict:
+    """Judge an `instaslice-payload paged` report: "paged" fails unless
+    `max_err` is a numeric zero, `max_rel` is a real number in [0, 2**-8],
+    `batch`, `hq`, `hkv`, `len`, `iters`, `items` are integer counts >= 1 and
+    `page` is 32, 64, 128 or 256. `kv_gb_per_s`, `steps_per_s` and `tok_per_s`
+    are carried and never judged. Pure; the report's own `ok` is not trusted.
+    ValueError on a profile name that does not parse."""
+    return _judge_one(report, profile_name, "paged",
+                      lambda r: _attn_fields_clean(r, ATTN_MAX_REL)
+                      and _counts_from_one(r, ("items",))
+                      and _is_count(r.get("page")) and r["page"] in PAGED_PAGES)
+
+
+def run_paged(profile_name: str, env: Optional[Dict[str, str]] = None,
+              runner: Callable = subprocess.run) -> dict:
+    """Run `instaslice-payload paged` (default shape, page size and
+    iterations) in a fresh child with `env` and judge its report, with the
+    same contract as `run_attn`: every way the child can fail comes back as
+    `ok: False` with a `reason`, and only an unparseable profile name raises
+    (ValueError)."""
+    parse_profile_name(profile_name)
+    return _run_child(profile_name, ["paged"], CHILD_TIMEOUT_S, "max_err",
+                      lambda report: judge_paged(report, profile_name),
                       env, runner)
 
 
