@@ -20,7 +20,8 @@
     python -m instaslice_amd cordon     --store HOST:PORT --node N [--uncordon]
     python -m instaslice_amd payload    [info|vecadd|membw|busy|census|gemm|
                                          dgemm|igemm|mxgemm|mx4gemm|moe|attn|
-                                         paged|prefill|memcheck|verify] ...
+                                         paged|paged8|prefill|memcheck|
+                                         verify] ...
     python -m instaslice_amd verify     --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
     python -m instaslice_amd memcheck   --profile NAME [--gb G | --fraction F]
@@ -39,6 +40,8 @@
     python -m instaslice_amd attn       --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
     python -m instaslice_amd paged      --profile NAME
+                                        [--visible-devices UUID_OR_INDEX]
+    python -m instaslice_amd paged8     --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
     python -m instaslice_amd prefill   --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
@@ -463,6 +466,13 @@ def cmd_paged(args) -> int:
     return _probe(args, "run_paged")
 
 
+def cmd_paged8(args) -> int:
+    """Run the paged decode attention payload over an FP8 KV cache inside the
+    visible partition and judge it against the requested profile; prints the
+    judged JSON, exit 0 iff ok."""
+    return _probe(args, "run_paged8")
+
+
 def cmd_prefill(args) -> int:
     """Run the causal prefill attention payload inside the visible partition
     and judge it against the requested profile; prints the judged JSON, exit
@@ -660,6 +670,17 @@ def main(argv=None) -> int:
                    help="ROCR_VISIBLE_DEVICES for the probe (partition UUID "
                         "or index); default: inherit the environment")
     p.set_defaults(fn=cmd_paged)
+
+    p = sub.add_parser("paged8",
+                       help="check and time paged decode attention over an "
+                            "FP8 (e4m3, per-head scale) KV cache beside the "
+                            "bf16 kernel in the visible partition, judge it "
+                            "against a profile")
+    p.add_argument("--profile", required=True, help="e.g. cpx-1x36")
+    p.add_argument("--visible-devices", default=None,
+                   help="ROCR_VISIBLE_DEVICES for the probe (partition UUID "
+                        "or index); default: inherit the environment")
+    p.set_defaults(fn=cmd_paged8)
 
     p = sub.add_parser("prefill",
                        help="check and time causal prefill attention (the "

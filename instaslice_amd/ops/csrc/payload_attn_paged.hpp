@@ -74,8 +74,9 @@ struct AttnPagedPlan {
   std::vector<int> seq;    // 2 per sequence: first part, parts (items * 4)
 };
 
-__host__ __device__ inline int attn_paged_chunks(int len) {
-  return (len + kAttnChunk - 1) / kAttnChunk;
+// `chunk` keys: 32 for the bf16 cache, 64 for the fp8 one (payload_attn_fp8.hpp)
+__host__ __device__ inline int attn_paged_chunks(int len, int chunk = kAttnChunk) {
+  return (len + chunk - 1) / chunk;
 }
 
 // chunk where item j of n starts in a sequence of c chunks (j = n: c)
@@ -84,21 +85,24 @@ __host__ __device__ inline int attn_paged_cut(int c, int n, int j) {
 }
 
 // The specification of attn_paged_plan_kernel. lens[b] >= 1, target in 1 ..
-// 4096, sum_b ceil(lens[b] / 32) below 2^31.
-inline AttnPagedPlan attn_paged_plan(const int* lens, int B, int target) {
+// 4096, chunk 32 or 64, sum_b ceil(lens[b] / chunk) below 2^31.
+inline AttnPagedPlan attn_paged_plan(const int* lens, int B, int target,
+                                     int chunk = kAttnChunk) {
   if (B < 1 || target < 1 || target > kAttnPagedMaxTarget)
     throw std::invalid_argument("attn_paged_plan: B >= 1 and target in 1 .. 4096");
+  if (chunk != 32 && chunk != 64)
+    throw std::invalid_argument("attn_paged_plan: chunk must be 32 or 64");
   long long C = 0;
   for (int b = 0; b < B; ++b) {
     if (lens[b] < 1) throw std::invalid_argument("attn_paged_plan: lengths must be >= 1");
-    C += attn_paged_chunks(lens[b]);
+    C += attn_paged_chunks(lens[b], chunk);
   }
   if (C > INT32_MAX) throw std::invalid_argument("attn_paged_plan: too many chunks");
   const int per = static_cast<int>((C + target - 1) / target);
   AttnPagedPlan p;
   int first = 0;
   for (int b = 0; b < B; ++b) {
-    const int c = attn_paged_chunks(lens[b]), n = (c + per - 1) / per;
+    const int c = attn_paged_chunks(lens[b], chunk), n = (c + per - 1) / per;
     p.seq.push_back(first * kAttnWaves);
     p.seq.push_back(n * kAttnWaves);
     for (int j = 0; j < n; ++j) {
@@ -114,17 +118,18 @@ inline AttnPagedPlan attn_paged_plan(const int* lens, int B, int target) {
 // ---- kernels -------------------------------------------------------------
 
 // One workgroup. lens: [B], clamped to 0 .. Lmax. items: target + B entries.
-// seq: [B]. nitems: one int.
+// seq: [B]. nitems: one int. The plan counts chunks of `chunk` keys.
 __global__ __launch_bounds__(kBlock) void attn_paged_plan_kernel(
     const int* __restrict__ lens, int B, int Lmax, int target,
-    int4* __restrict__ items, int2* __restrict__ seq, int* __restrict__ nitems) {
+    int4* __restrict__ items, int2* __restrict__ seq, int* __restrict__ nitems,
+    int chunk = kAttnChunk) {
   __shared__ int scan[kBlock];
   __shared__ int carry;
   const int tid = threadIdx.x;
 
   int mine = 0;  // chunks of the sequences tid, tid + 256, ...
   for (int b = tid; b < B; b += kBlock)
-    mine += attn_paged_chunks(min(max(lens[b], 0), Lmax));
+    mine += attn_paged_chunks(min(max(lens[b], 0), Lmax), chunk);
   scan[tid] = mine;
   if (tid == 0) carry = 0;
   __syncthreads();
@@ -140,7 +145,7 @@ __global__ __launch_bounds__(kBlock) void attn_paged_plan_kernel(
 
   for (int b0 = 0; b0 < B; b0 += kBlock) {  // block-uniform
     const int b = b0 + tid;
-    const int c = b < B ? attn_paged_chunks(min(max(lens[b], 0), Lmax)) : 0;
+    const int c = b < B ? attn_paged_chunks(min(max(lens[b], 0), Lmax), chunk) : 0;
     const int n = (c + per - 1) / per;
     scan[tid] = n;
     __syncthreads();
@@ -453,7 +458,8 @@ struct AttnPagedProblem : AttnShape {
 
   // workgroups = 0: items for half the visible CUs, the count that
   // profiles/attn_probe.md found best for the contiguous kernel
-  void alloc() {
+  // kv_bytes: per cache element, 2 for bf16
+  void alloc(size_t kv_bytes = sizeof(uint16_t)) {
     HIP_CHECK(hipSetDevice(device));
     if (target == 0) {
       int cus = 0;
@@ -463,8 +469,8 @@ struct AttnPagedProblem : AttnShape {
     }
     const size_t parts = static_cast<size_t>(max_items()) * kAttnWaves * Hq;
     dq.alloc(static_cast<size_t>(B) * Hkv * 16 * kAttnD * sizeof(uint16_t));
-    dk.alloc(pool_elems() * sizeof(uint16_t));
-    dvt.alloc(pool_elems() * sizeof(uint16_t));
+    dk.alloc(pool_elems() * kv_bytes);
+    dvt.alloc(pool_elems() * kv_bytes);
     dtable.alloc(static_cast<size_t>(B) * W * sizeof(int));
     dlens.alloc(static_cast<size_t>(B) * sizeof(int));
     ditems.alloc(static_cast<size_t>(max_items()) * sizeof(int4));
@@ -551,17 +557,18 @@ inline std::vector<int> attn_paged_lens(int B, int L, bool ragged) {
 
 // dense (B, Hkv, L, 128), L >= lens[b] -> the pool (P, Hkv, page, 128) under
 // the table: the keys below lens[b], and `stale` at the further keys of the
-// last chunk that is read. Nothing else of the pool is written.
-inline void attn_paged_scatter(const float* dense, float* pool, const int* table,
+// last chunk (of `chunk` keys) that is read. Nothing else of the pool is written.
+template <class T>
+inline void attn_paged_scatter(const T* dense, T* pool, const int* table,
                                const int* lens, int B, int Hkv, int L, int page, int W,
-                               float stale) {
+                               T stale, int chunk = kAttnChunk) {
   for (int b = 0; b < B; ++b) {
-    const int read = static_cast<int>(round_up(lens[b], kAttnChunk));
+    const int read = static_cast<int>(round_up(lens[b], chunk));
     for (int g = 0; g < Hkv; ++g)
       for (int t = 0; t < read; ++t) {
         const size_t pg = static_cast<size_t>(table[static_cast<size_t>(b) * W + t / page]);
-        float* dst = pool + ((pg * Hkv + g) * page + t % page) * kAttnD;
-        const float* src =
+        T* dst = pool + ((pg * Hkv + g) * page + t % page) * kAttnD;
+        const T* src =
             dense + ((static_cast<size_t>(b) * Hkv + g) * L + std::min(t, L - 1)) * kAttnD;
         for (int d = 0; d < kAttnD; ++d) dst[d] = t < lens[b] ? src[d] : stale;
       }

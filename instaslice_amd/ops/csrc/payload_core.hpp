@@ -68,6 +68,13 @@
 //                scan) writes in every launch; exact-checked, bound-checked
 //                and timed: how a serving stack really keeps its cache
 //                (payload_attn_paged.hpp, included below)
+//   paged8       paged decode attention over an FP8 cache: OCP e4m3 codes with a
+//                scale per kv head, 64-key chunks behind 16-byte loads, widened
+//                to bf16 in registers two at a time in front of the bf16 MFMA,
+//                the scales folded into the score factor and the output
+//                accumulators; exact-checked, bound-checked and timed against
+//                the bf16 kernel: half the bytes per key
+//                (payload_attn_fp8.hpp, included below)
 //   prefill     causal prefill attention over a whole prompt (grouped-query,
 //                head dim 128): K and V tiles staged through swizzled,
 //                double-buffered LDS and shared by the workgroup's waves, both
@@ -634,6 +641,11 @@ inline int device_count() {
 // paged decode attention payload: the decode one's layout, patterns, chunk
 // arithmetic, reference row and bound
 #include "payload_attn_paged.hpp"
+
+// paged decode attention over an FP8 (e4m3) cache: the paged one's plan,
+// combine kernel, problem struct and host helpers, the MXFP8 payload's e4m3
+// conversions
+#include "payload_attn_fp8.hpp"
 
 // prefill attention payload: the decode one's head dim, patterns, scale and
 // shared host pieces

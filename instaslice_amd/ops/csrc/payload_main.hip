@@ -98,6 +98,19 @@
 //                                             or absent: auto) the count it
 //                                             aims at; exit 1 unless max_err
 //                                             == 0 and max_rel <= 2^-8
+//   instaslice-payload paged8 [B HQ HKV L [PAGE [ITERS [WORKGROUPS]]]]
+//                                             paged with an FP8 cache: OCP e4m3
+//                                             codes and a scale per kv head,
+//                                             widened to bf16 in registers (PAGE
+//                                             64, 128 or 256): the self-check at
+//                                             4 8 2 300, page 64, then the timed
+//                                             run; the `paged` report plus
+//                                             "us" per step, "bf16_us" (`paged`
+//                                             on the same shape in the same
+//                                             process) and "quant_rel" (the
+//                                             format's error on dense data,
+//                                             reported only); exit 1 unless
+//                                             max_err == 0 and max_rel <= 2^-8
 //   instaslice-payload prefill [B HQ HKV L [ITERS [CAUSAL [PATTERN]]]]
 //                                             causal prefill attention (bf16
 //                                             MFMA, K and V tiles through LDS,
@@ -392,6 +405,26 @@ int main(int argc, char** argv) {
           page, iters, r.items, r.kv_gb_s, r.steps_per_s, r.tok_per_s, json_num(max_err),
           json_num(c.max_rel));
       return ok ? 0 : 1;
+    } else if (std::strcmp(cmd, "paged8") == 0) {
+      AttnArgs a{32, 64, 8, 4096};
+      a.parse(argc, argv);
+      int page = argc > 6 ? std::atoi(argv[6]) : 64;
+      int iters = argc > 7 ? std::atoi(argv[7]) : 10;
+      int workgroups = argc > 8 ? std::atoi(argv[8]) : 0;
+      AttnCheck c = run_attn_paged_fp8_check(4, 8, 2, 300, 64);
+      AttnPaged8Result r =
+          run_attn_paged_fp8(a.b, a.hq, a.hkv, a.len, page, iters, false, workgroups);
+      double max_err = r.max_err > c.max_err ? r.max_err : c.max_err;
+      bool ok = max_err == 0.0 && c.max_rel <= kAttnRelBound;
+      a.print_head("paged8", ok);
+      std::printf(
+          "\"page\": %d, \"iters\": %d, \"items\": %d, \"us\": %.2f, "
+          "\"bf16_us\": %.2f, \"kv_gb_per_s\": %.1f, \"steps_per_s\": %.1f, "
+          "\"tok_per_s\": %.1f, \"quant_rel\": %g, \"max_err\": %g, "
+          "\"max_rel\": %g}\n",
+          page, iters, r.items, r.us, r.bf16_us, r.kv_gb_s, r.steps_per_s, r.tok_per_s,
+          json_num(r.quant_rel), json_num(max_err), json_num(c.max_rel));
+      return ok ? 0 : 1;
     } else if (std::strcmp(cmd, "prefill") == 0) {
       AttnArgs a{8, 64, 8, 4096};
       a.parse(argc, argv);
@@ -457,7 +490,8 @@ int main(int argc, char** argv) {
       //   vecadd <n> | busy <ms> | gemm [M N K] | dgemm [M N K] |
       //   igemm [M N K] | mxgemm [M N K] | mx4gemm [M N K] |
       //   moe [T N K E TOPK] | attn [B HQ HKV L] | paged [B HQ HKV L [PAGE]] |
-      //   prefill [B HQ HKV L] | memcheck [BYTES] | ping | quit
+      //   paged8 [B HQ HKV L [PAGE]] | prefill [B HQ HKV L] | memcheck [BYTES] |
+      //   ping | quit
       std::string line;
       while (std::getline(std::cin, line)) {
         std::istringstream iss(line);
@@ -489,6 +523,16 @@ int main(int argc, char** argv) {
             std::snprintf(extra, sizeof(extra), "\"page\": %d, ", page);
             print_attn_check("paged", a,
                              run_attn_paged_check(a.b, a.hq, a.hkv, a.len, page), extra);
+          } else if (verb == "paged8") {
+            AttnArgs a{4, 8, 2, 300};
+            a.parse(iss);
+            int page = 64, tp;
+            if (iss >> tp) page = tp;
+            char extra[32];
+            std::snprintf(extra, sizeof(extra), "\"page\": %d, ", page);
+            print_attn_check("paged8", a,
+                             run_attn_paged_fp8_check(a.b, a.hq, a.hkv, a.len, page),
+                             extra);
           } else if (verb == "prefill") {
             AttnArgs a{1, 4, 2, 200};
             a.parse(iss);

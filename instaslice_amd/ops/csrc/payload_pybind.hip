@@ -169,6 +169,15 @@ i8_array int8_operand(const char* who, const char* what, const py::object& x) {
   return i8_array::ensure(x);
 }
 
+// a pool of e4m3 codes of the fp8 attention entry: uint8 and nothing else, for
+// the same reason
+u8_array uint8_operand(const char* who, const char* what, const py::object& x) {
+  if (!py::isinstance<py::array>(x) ||
+      !py::reinterpret_borrow<py::array>(x).dtype().is(py::dtype::of<uint8_t>()))
+    throw py::type_error(std::string(who) + ": " + what + " must be a uint8 array");
+  return u8_array::ensure(x);
+}
+
 // (M, N, K) of the INT8 GEMM entries: gemm_dims plus the K limit
 std::array<int, 3> igemm_dims(const char* who, const i8_array& a, const i8_array& b) {
   auto dims = gemm_dims(who, a, b);
@@ -321,7 +330,8 @@ py::dict attn_timed_dict(int batch, int hq, int hkv, int length, int iters) {
 
 PYBIND11_MODULE(_payload, m) {
   m.doc() = "gfx950 HIP payload kernels (vecadd / membw / busy / xcd census / gemm / "
-            "dgemm / igemm / mxgemm / mx4gemm / moe / memcheck / attn / paged / prefill)";
+            "dgemm / igemm / mxgemm / mx4gemm / moe / memcheck / attn / paged / paged8 / "
+            "prefill)";
 
   m.def("device_count", &payload::device_count,
         "Number of visible HIP devices (0 if no GPU/driver)");
@@ -1130,13 +1140,13 @@ PYBIND11_MODULE(_payload, m) {
 
   m.def(
       "attn_paged_plan",
-      [](py::object lens_, int target) {
+      [](py::object lens_, int target, int chunk) {
         auto arr = paged_ints("attn_paged_plan", "lens", lens_, 1);
         if (arr.shape(0) < 1 || arr.shape(0) > 65535)
           throw py::value_error("attn_paged_plan: lens must hold 1 .. 65535 lengths");
         const std::vector<int> lens = paged_narrow(arr);
-        const payload::AttnPagedPlan plan =
-            payload::attn_paged_plan(lens.data(), static_cast<int>(lens.size()), target);
+        const payload::AttnPagedPlan plan = payload::attn_paged_plan(
+            lens.data(), static_cast<int>(lens.size()), target, chunk);
         py::array_t<int32_t> items({static_cast<py::ssize_t>(plan.items.size() / 3),
                                     py::ssize_t{3}});
         py::array_t<int32_t> seq({static_cast<py::ssize_t>(lens.size()), py::ssize_t{2}});
@@ -1144,12 +1154,12 @@ PYBIND11_MODULE(_payload, m) {
         std::copy(plan.seq.begin(), plan.seq.end(), seq.mutable_data());
         return py::make_tuple(items, seq);
       },
-      py::arg("lens"), py::arg("target"),
-      "the work plan of the paged decode kernel, computed on the host with the "
+      py::arg("lens"), py::arg("target"), py::arg("chunk") = payload::kAttnChunk,
+      "the work plan of the paged decode kernels, computed on the host with the "
       "arithmetic of the device's plan kernel: (items int32 (n,3) of (sequence, "
-      "chunk_begin, chunk_end) over 32-key chunks, seq int32 (B,2) of (first "
-      "partial, partials) per sequence); n <= target + B, target in 1 .. 4096; "
-      "host only, no GPU");
+      "chunk_begin, chunk_end) over chunks of `chunk` keys, 32 for the bf16 cache "
+      "and 64 for the fp8 one, seq int32 (B,2) of (first partial, partials) per "
+      "sequence); n <= target + B, target in 1 .. 4096; host only, no GPU");
 
   m.def(
       "run_attn_paged_check",
@@ -1206,6 +1216,130 @@ PYBIND11_MODULE(_payload, m) {
       "below the lengths; items is the plan's item count; contiguous=True times "
       "the contiguous kernel on the same lengths and data instead (length a "
       "multiple of page), for comparison");
+
+  // ---- paged decode attention over an fp8 cache ------------------------------
+
+  m.def(
+      "attn_paged_decode_fp8",
+      [](f32_array q, py::object k_codes_, py::object v_codes_, f32_array k_scale,
+         f32_array v_scale, py::object table_, py::object lens_, py::object scale,
+         int workgroups, int device) {
+        const char* who = "attn_paged_decode_fp8";
+        const std::string w(who);
+        auto k_codes = uint8_operand(who, "k_codes", k_codes_);
+        auto v_codes = uint8_operand(who, "v_codes", v_codes_);
+        auto table = paged_ints(who, "table", table_, 2);
+        auto lens_arr = paged_ints(who, "lens", lens_, 1);
+        if (q.ndim() != 3) throw py::value_error(w + ": q must be (B,Hq,128)");
+        if (k_codes.ndim() != 4 || v_codes.ndim() != 4)
+          throw py::value_error(w + ": k_codes and v_codes must be (P,Hkv,page,128)");
+        if (q.shape(2) != payload::kAttnD || k_codes.shape(3) != payload::kAttnD)
+          throw py::value_error(w + ": head dim must be 128");
+        for (int i = 0; i < 4; ++i)
+          if (k_codes.shape(i) != v_codes.shape(i))
+            throw py::value_error(w + ": k_codes and v_codes differ in shape");
+        const py::ssize_t B = q.shape(0), Hq = q.shape(1), P = k_codes.shape(0),
+                          Hkv = k_codes.shape(1), page = k_codes.shape(2),
+                          W = table.shape(1);
+        if (table.shape(0) != B || lens_arr.shape(0) != B)
+          throw py::value_error(w + ": table must be (B,W) and lens (B,)");
+        scale_vector(who, "k_scale", k_scale, static_cast<int>(Hkv));
+        scale_vector(who, "v_scale", v_scale, static_cast<int>(Hkv));
+        payload::attn_paged_fp8_shape(B, Hq, Hkv, page, W, P, workgroups);
+        const std::vector<int> tab = paged_narrow(table), lens = paged_narrow(lens_arr);
+        const float sc = attn_scale(who, scale);
+        const float* pq = q.data();
+        const uint8_t* pk = k_codes.data();
+        const uint8_t* pv = v_codes.data();
+        const float* pks = k_scale.data();
+        const float* pvs = v_scale.data();
+        py::array_t<float> o({B, Hq, static_cast<py::ssize_t>(payload::kAttnD)});
+        float* po = o.mutable_data();
+        {
+          py::gil_scoped_release rel;
+          payload::attn_paged_decode_fp8(pq, pk, pv, pks, pvs, tab.data(), lens.data(), po,
+                                         static_cast<int>(B), static_cast<int>(Hq),
+                                         static_cast<int>(Hkv), static_cast<int>(page),
+                                         static_cast<int>(W), static_cast<int>(P), sc,
+                                         workgroups, device);
+        }
+        return o;
+      },
+      py::arg("q"), py::arg("k_codes"), py::arg("v_codes"), py::arg("k_scale"),
+      py::arg("v_scale"), py::arg("table"), py::arg("lens"),
+      py::arg("scale") = py::none(), py::arg("workgroups") = 0, py::arg("device") = 0,
+      "o (B,Hq,128) float32: attn_paged_decode over an FP8 cache. k_codes and "
+      "v_codes (P,Hkv,page,128) uint8 hold OCP e4m3 codes (to_e4m3(x / s)), page "
+      "64, 128 or 256; k_scale and v_scale (Hkv,) float32, finite and > 0, are the "
+      "scales s per kv head: K = k_scale[g] * e4m3(k_codes), likewise V. The codes "
+      "are widened to bf16 exactly, in registers, in front of the bf16 MFMA; the "
+      "scales are folded into the score factor and the output. Only the 64-key "
+      "chunks below ceil(lens[b]/64) are read; they must hold no NaN code (0x7F, "
+      "0xFF). table, lens, scale and workgroups as in attn_paged_decode. TypeError "
+      "on pools that are not uint8 or a floating table or lens, ValueError on an "
+      "unsupported shape, scale, length, table entry, NaN code or non-finite q, "
+      "all before any device work");
+
+  m.def(
+      "run_attn_paged_fp8_check",
+      [](int batch, int hq, int hkv, int length, int page, int workgroups, bool ragged,
+         int device) {
+        payload::attn_paged_fp8_shape(batch, hq, hkv, page, 1, 1, workgroups);
+        if (length < 1 || length > (1 << 24))
+          throw py::value_error("run_attn_paged_fp8_check: length must be in 1 .. 2^24");
+        payload::AttnCheck r;
+        {
+          py::gil_scoped_release rel;
+          r = payload::run_attn_paged_fp8_check(batch, hq, hkv, length, page, workgroups,
+                                                ragged, device);
+        }
+        return attn_check_dict(r);
+      },
+      py::arg("batch"), py::arg("hq"), py::arg("hkv"), py::arg("length"),
+      py::arg("page") = 64, py::arg("workgroups") = 0, py::arg("ragged") = true,
+      py::arg("device") = 0,
+      "fp8 paged decode attention self-check. ragged=True: sequence b takes entry b "
+      "% 8 of (length, 1, 33, 63, 64, 65, 2 page + 1, a multiple of 64), each at "
+      "most `length`; otherwise every sequence has `length` keys. Scrambled table, "
+      "NaN codes in everything that must not be read, 448 at the stale keys of a "
+      "read chunk: max_err of the e4m3 selection pattern (expect exactly 0) and "
+      "max_rel = max |o - fp64 ref on the dequantised values| / max |v| of a dense "
+      "pattern (expect <= 2^-8)");
+
+  m.def(
+      "run_attn_paged_fp8",
+      [](int batch, int hq, int hkv, int length, int page, int iters, bool ragged,
+         int workgroups, int device) {
+        payload::attn_paged_fp8_shape(batch, hq, hkv, page, 1, 1, workgroups);
+        if (iters < 1) throw py::value_error("run_attn_paged_fp8: iters must be >= 1");
+        payload::AttnPaged8Result r;
+        {
+          py::gil_scoped_release rel;
+          r = payload::run_attn_paged_fp8(batch, hq, hkv, length, page, iters, ragged,
+                                          workgroups, device);
+        }
+        py::dict d = attn_timed_dict(batch, hq, hkv, length, iters);
+        d["page"] = page;
+        d["ragged"] = ragged;
+        d["items"] = r.items;
+        d["us"] = r.us;
+        d["bf16_us"] = r.bf16_us;
+        d["kv_gb_per_s"] = r.kv_gb_s;
+        d["steps_per_s"] = r.steps_per_s;
+        d["tok_per_s"] = r.tok_per_s;
+        d["quant_rel"] = r.quant_rel;
+        d["max_err"] = r.max_err;
+        return d;
+      },
+      py::arg("batch") = 32, py::arg("hq") = 64, py::arg("hkv") = 8,
+      py::arg("length") = 4096, py::arg("page") = 64, py::arg("iters") = 10,
+      py::arg("ragged") = false, py::arg("workgroups") = 0, py::arg("device") = 0,
+      "timed fp8 paged decode attention on the e4m3 selection pattern (pool filled "
+      "on the device; plan, decode and combine per launch), 16 output rows checked "
+      "exactly; us is the time of a step, kv_gb_per_s counts one byte per element "
+      "of the keys below the lengths; bf16_us is run_attn_paged on the same "
+      "arguments in the same process; quant_rel is the error against fp64 on "
+      "unquantised dense data, a property of the format that is never judged");
 
   // ---- prefill attention -----------------------------------------------------
 

@@ -97,6 +97,16 @@ the same 2**-8, the counts (`items` among them) are integers >= 1 and `page`
 is 32, 64, 128 or 256. `attn` addresses a chunk as base + chunk * 8 KiB, so a
 partition whose scalar-load-then-vector-load path is wrong passes it and fails
 here. Rates are carried in the report and never judged.
+
+So has the cache a serving stack keeps when it wants the bytes halved.
+`run_paged8` runs `instaslice-payload paged8` (the paged attention over OCP
+e4m3 codes with a scale per kv head, widened to bf16 in registers in front of
+the bf16 MFMA; the self-check with NaN codes in everything that must not be
+read, then a timed run beside the bf16 kernel) and `judge_paged8` fails
+"paged8" on the same terms as `judge_paged`, with `page` 64, 128 or 256.
+Nothing else puts 8-bit loads and the fp8 conversion instructions in front of
+the matrix cores. `quant_rel`, the error of the format itself, is carried and
+never judged.
 """
 
 from __future__ import annotations
@@ -495,6 +505,39 @@ def run_paged(profile_name: str, env: Optional[Dict[str, str]] = None,
     parse_profile_name(profile_name)
     return _run_child(profile_name, ["paged"], CHILD_TIMEOUT_S, "max_err",
                       lambda report: judge_paged(report, profile_name),
+                      env, runner)
+
+
+# ---- paged8 -----------------------------------------------------------------
+
+PAGED8_PAGES = (64, 128, 256)
+
+
+def judge_paged8(report: dict, profile_name: str) -> dict:
+    """Judge an `instaslice-payload paged8` report: "paged8" fails unless
+    `max_err` is a numeric zero, `max_rel` is a real number in [0, 2**-8]
+    (widening e4m3 to bf16 is exact, so the bound is `judge_paged`'s),
+    `batch`, `hq`, `hkv`, `len`, `iters`, `items` are integer counts >= 1 and
+    `page` is 64, 128 or 256. `us`, `bf16_us`, `kv_gb_per_s`, `steps_per_s`,
+    `tok_per_s` and `quant_rel` (the error of the format itself) are carried
+    and never judged. Pure; the report's own `ok` is not trusted. ValueError
+    on a profile name that does not parse."""
+    return _judge_one(report, profile_name, "paged8",
+                      lambda r: _attn_fields_clean(r, ATTN_MAX_REL)
+                      and _counts_from_one(r, ("items",))
+                      and _is_count(r.get("page")) and r["page"] in PAGED8_PAGES)
+
+
+def run_paged8(profile_name: str, env: Optional[Dict[str, str]] = None,
+               runner: Callable = subprocess.run) -> dict:
+    """Run `instaslice-payload paged8` (default shape, page size and
+    iterations) in a fresh child with `env` and judge its report, with the
+    same contract as `run_paged`: every way the child can fail comes back as
+    `ok: False` with a `reason`, and only an unparseable profile name raises
+    (ValueError)."""
+    parse_profile_name(profile_name)
+    return _run_child(profile_name, ["paged8"], CHILD_TIMEOUT_S, "max_err",
+                      lambda report: judge_paged8(report, profile_name),
                       env, runner)
 
 
