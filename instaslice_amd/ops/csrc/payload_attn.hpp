@@ -149,10 +149,109 @@ __device__ __forceinline__ short attn_p_bf16(float f) {
   return static_cast<short>(u >> 16);
 }
 
+// ---- the chunk step of the two bf16 decode kernels --------------------------
+//
+// attn_decode_kernel and attn_paged_decode_kernel (payload_attn_paged.hpp)
+// differ in how a chunk is found and how the work is split; what they do with
+// a chunk stands here once. The e4m3 kernel (payload_attn_fp8.hpp) repeats
+// these steps at 64 keys per chunk in a body of its own.
+
+// B fragments of Q^T of (sequence, kv head) bg: lane l holds q[head l & 15][d =
+// 32 s + 8 (l >> 4) + j]
+__device__ __forceinline__ void attn_load_q(bf16x8 (&fqt)[kAttnD / 32],
+                                            const uint16_t* __restrict__ q, size_t bg,
+                                            int fr, int fq) {
+  const uint16_t* qb = q + (bg * 16 + fr) * kAttnD + fq * 8;
+#pragma unroll
+  for (int s = 0; s < kAttnD / 32; ++s)
+    fqt[s] = *reinterpret_cast<const bf16x8*>(qb + s * 32);
+}
+
+// the eight fragments of a K or V chunk image, 512 elements apart; p is the
+// lane's first one. K: fragment 4 t + s is (QK tile t, d-step s). V: fragment dt
+// is d-tile dt.
+__device__ __forceinline__ void attn_load_image(bf16x8 (&r)[8], const uint16_t* p) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) r[i] = *reinterpret_cast<const bf16x8*>(p + i * 512);
+}
+
+// S^T = K Q^T of a chunk: two tiles, four d-steps each
+__device__ __forceinline__ void attn_qk(const bf16x8 (&fk)[8],
+                                        const bf16x8 (&fqt)[kAttnD / 32], f32x4 (&st)[2]) {
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    st[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < kAttnD / 32; ++s)
+      st[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fk[t * 4 + s], fqt[s], st[t], 0, 0, 0);
+  }
+}
+
+// What follows the QK tiles of the chunk at key c0. Register r of tile t is key
+// c0 + 8 fq + 4 t + r, so the lane's weight j is key c0 + 8 fq + j: masked by
+// index, the chunk maximum taken over the four lane quarters, m and l (this
+// lane's keys only) updated, the weights rounded to bf16 as the PV B fragment;
+// then o is rescaled and takes the PV product with the chunk's V fragments.
+__device__ __forceinline__ void attn_softmax_pv(const f32x4 (&st)[2],
+                                                const bf16x8 (&fv)[8], int c0, int fq,
+                                                int len, float c2, float& m, float& l,
+                                                f32x4 (&o)[kAttnD / 16]) {
+  float sc[8];
+  float cm = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int key = c0 + 8 * fq + j;
+    sc[j] = key < len ? st[j >> 2][j & 3] * c2 : -INFINITY;
+    cm = fmaxf(cm, sc[j]);
+  }
+  cm = fmaxf(cm, __shfl_xor(cm, 16));
+  cm = fmaxf(cm, __shfl_xor(cm, 32));
+
+  const float mn = fmaxf(m, cm);
+  const float ms = mn == -INFINITY ? 0.f : mn;  // never (-inf) - (-inf)
+  const float alpha = __builtin_amdgcn_exp2f(m - ms);  // m = -inf: 0
+  m = mn;
+
+  bf16x8 fp;
+  float sum = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float p = __builtin_amdgcn_exp2f(sc[j] - ms);
+    sum += p;  // l takes the unrounded weight
+    fp[j] = attn_p_bf16(p);
+  }
+  l = l * alpha + sum;
+
+#pragma unroll
+  for (int dt = 0; dt < kAttnD / 16; ++dt) {
+    o[dt] *= alpha;
+    o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fv[dt], fp, o[dt], 0, 0, 0);
+  }
+}
+
+// One wave's unnormalised (m, l, o[128]) as partial `part` of its head, for the
+// lanes of a real head (fr < G): pm, pl [part], po [part * 128 + d]. l is the
+// head's, summed over its four lanes. C/D map of o: col (head) = lane & 15,
+// row (d) = 16 dt + 4 (lane >> 4) + reg.
+__device__ __forceinline__ void attn_write_partial(float* __restrict__ pm,
+                                                   float* __restrict__ pl,
+                                                   float* __restrict__ po, size_t part,
+                                                   int fq, float m, float l,
+                                                   const f32x4 (&o)[kAttnD / 16]) {
+  if (fq == 0) {
+    pm[part] = m;
+    pl[part] = l;
+  }
+#pragma unroll
+  for (int dt = 0; dt < kAttnD / 16; ++dt)
+    *reinterpret_cast<f32x4*>(po + part * kAttnD + dt * 16 + fq * 4) = o[dt];
+}
+
 // q: [B][Hkv][16][128] bf16, rows G .. 15 zero. k, vt: [B][Hkv][Lp / 32] chunk
 // images of 4096 bf16 (attn_k_off, attn_v_off). lens: [B]. Partials of head row = b Hq + h, part
 // = split * 4 + wave, P = 4 * gridDim.x: pm, pl [row * P + part], po [(row * P
-// + part) * 128 + d]. c2 = scale * log2(e). grid = (splits, Hkv, B).
+// + part) * 128 + d]. c2 = scale * log2(e). grid = (splits, Hkv, B). The split
+// arithmetic and the contiguous addressing are this kernel's own.
 __global__ __launch_bounds__(kBlock) void attn_decode_kernel(
     const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
     const uint16_t* __restrict__ vt, const int* __restrict__ lens,
@@ -171,19 +270,12 @@ __global__ __launch_bounds__(kBlock) void attn_decode_kernel(
   const int ch_end = min(nch, ch_begin + per);  // <= ch_begin: an empty split
 
   const size_t bg = static_cast<size_t>(b) * Hkv + g;
-
-  // B fragments of Q^T: lane l holds q[head l & 15][d = 32 s + 8 (l >> 4) + j]
   bf16x8 fqt[kAttnD / 32];
-  {
-    const uint16_t* qb = q + (bg * 16 + fr) * kAttnD + fq * 8;
-#pragma unroll
-    for (int s = 0; s < kAttnD / 32; ++s)
-      fqt[s] = *reinterpret_cast<const bf16x8*>(qb + s * 32);
-  }
+  attn_load_q(fqt, q, bg, fr, fq);
 
-  // A fragments, 512 elements apart. K: row fr of QK tile t is key 8 (fr >> 2)
-  // + 4 t + (fr & 3) of the chunk, d = 32 s + 8 fq + j. V^T: row fr of d-tile dt
-  // is d = 16 dt + fr, k index 8 fq + j is key 8 fq + j of the chunk.
+  // A fragments. K: row fr of QK tile t is key 8 (fr >> 2) + 4 t + (fr & 3) of
+  // the chunk, d = 32 s + 8 fq + j. V^T: row fr of d-tile dt is d = 16 dt + fr,
+  // k index 8 fq + j is key 8 fq + j of the chunk.
   const size_t img = bg * (Lp / kAttnChunk) * kAttnChunkElems + lane * 8;
   const uint16_t* kb = k + img;
   const uint16_t* vb = vt + img;
@@ -196,67 +288,18 @@ __global__ __launch_bounds__(kBlock) void attn_decode_kernel(
   // K runs one chunk ahead: its registers are free once the QK MFMAs have
   // read them, so the wave's next chunk is requested right there and arrives
   // under the softmax, the PV product and the next V loads. No extra registers.
-  bf16x8 fk[2][kAttnD / 32];
-  auto load_k = [&](int ch) {
-    const uint16_t* kc = kb + static_cast<size_t>(ch) * kAttnChunkElems;
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int s = 0; s < kAttnD / 32; ++s)
-        fk[t][s] = *reinterpret_cast<const bf16x8*>(kc + (t * 4 + s) * 512);
-  };
-  if (ch_begin + wave < ch_end) load_k(ch_begin + wave);
+  bf16x8 fk[8];
+  if (ch_begin + wave < ch_end)
+    attn_load_image(fk, kb + static_cast<size_t>(ch_begin + wave) * kAttnChunkElems);
 
   for (int ch = ch_begin + wave; ch < ch_end; ch += kAttnWaves) {  // wave-uniform
-    const int c0 = ch * kAttnChunk;
-    const uint16_t* vc = vb + static_cast<size_t>(ch) * kAttnChunkElems;
-    bf16x8 fv[kAttnD / 16];
-#pragma unroll
-    for (int dt = 0; dt < kAttnD / 16; ++dt)
-      fv[dt] = *reinterpret_cast<const bf16x8*>(vc + dt * 512);
-
-    f32x4 st[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int s = 0; s < kAttnD / 32; ++s)
-        st[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fk[t][s], fqt[s], st[t],
-                                                        0, 0, 0);
-
-    if (ch + kAttnWaves < ch_end) load_k(ch + kAttnWaves);
-
-    // register r of tile t: row 4 fq + r, that is key c0 + 8 fq + 4 t + r
-    float sc[8];
-    float cm = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int key = c0 + 8 * fq + j;
-      sc[j] = key < len ? st[j >> 2][j & 3] * c2 : -INFINITY;
-      cm = fmaxf(cm, sc[j]);
-    }
-    cm = fmaxf(cm, __shfl_xor(cm, 16));
-    cm = fmaxf(cm, __shfl_xor(cm, 32));
-
-    const float mn = fmaxf(m, cm);
-    const float ms = mn == -INFINITY ? 0.f : mn;  // never (-inf) - (-inf)
-    const float alpha = __builtin_amdgcn_exp2f(m - ms);  // m = -inf: 0
-    m = mn;
-
-    bf16x8 fp;
-    float sum = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float p = __builtin_amdgcn_exp2f(sc[j] - ms);
-      sum += p;  // l takes the unrounded weight
-      fp[j] = attn_p_bf16(p);
-    }
-    l = l * alpha + sum;
-
-#pragma unroll
-    for (int dt = 0; dt < kAttnD / 16; ++dt) {
-      o[dt] *= alpha;
-      o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fv[dt], fp, o[dt], 0, 0, 0);
-    }
+    bf16x8 fv[8];
+    attn_load_image(fv, vb + static_cast<size_t>(ch) * kAttnChunkElems);
+    f32x4 st[2];
+    attn_qk(fk, fqt, st);
+    if (ch + kAttnWaves < ch_end)
+      attn_load_image(fk, kb + static_cast<size_t>(ch + kAttnWaves) * kAttnChunkElems);
+    attn_softmax_pv(st, fv, ch * kAttnChunk, fq, len, c2, m, l, o);
   }
 
   // the head's l is spread over its four lanes; alpha was common to them
@@ -266,15 +309,7 @@ __global__ __launch_bounds__(kBlock) void attn_decode_kernel(
   if (fr < G) {
     const int Hq = Hkv * G, P = nsplit * kAttnWaves;
     const size_t row = static_cast<size_t>(b) * Hq + static_cast<size_t>(g) * G + fr;
-    const size_t part = row * P + split * kAttnWaves + wave;
-    if (fq == 0) {
-      pm[part] = m;
-      pl[part] = l;
-    }
-    // C/D map: col (head) = lane & 15, row (d) = 16 dt + 4 (lane >> 4) + reg
-#pragma unroll
-    for (int dt = 0; dt < kAttnD / 16; ++dt)
-      *reinterpret_cast<f32x4*>(po + part * kAttnD + dt * 16 + fq * 4) = o[dt];
+    attn_write_partial(pm, pl, po, row * P + split * kAttnWaves + wave, fq, m, l, o);
   }
 }
 
@@ -301,25 +336,37 @@ __global__ __launch_bounds__(kAttnD) void attn_combine_kernel(
   out[row * kAttnD + d] = acc / ls;  // the only division, and a true one
 }
 
-// Device-side fill of the selection pattern with full lengths (len = L) into
-// the cache layout, one fragment (8 bf16, 16 bytes) of each tensor per thread
-// and step; keys L .. Lp - 1 are zero. Small integers are exact in bf16, so
-// the top 16 bits of the float are the value.
+// Small integers are exact in bf16, so the top 16 bits of the float are the
+// value.
 __device__ __forceinline__ uint16_t attn_int_bf16(int v) {
   return static_cast<uint16_t>(__float_as_uint(static_cast<float>(v)) >> 16);
 }
 
-__global__ __launch_bounds__(kBlock) void attn_fill_kv_kernel(
-    uint16_t* __restrict__ k, uint16_t* __restrict__ vt, int Hkv, int L, int Lp,
-    size_t groups) {  // groups = B Hkv Lp 128 / 8, per tensor
+// Device-side fill of the selection pattern at the lengths lens[b], one
+// fragment (8 bf16, 16 bytes) of each tensor per thread and step, over `W <<
+// shift` logical chunks per (sequence, kv head); keys at and beyond lens[b] are
+// zero. With a table (payload_attn_paged.hpp: W pages of 32 << shift keys) the
+// image of logical chunk lc of (b, g) is found through it; with table null it
+// is at (b * Hkv + g) * chunks + lc, the contiguous layout (W = Lp / 32, shift
+// 0).
+__global__ __launch_bounds__(kBlock) void attn_paged_fill_kernel(
+    uint16_t* __restrict__ k, uint16_t* __restrict__ vt, const int* __restrict__ table,
+    const int* __restrict__ lens, int Hkv, int W, int shift,
+    size_t groups) {  // groups = B Hkv (W << shift) 4096 / 8, per tensor
   size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
   const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
-  const size_t chunks = static_cast<size_t>(Lp / kAttnChunk);
+  const size_t chunks = static_cast<size_t>(W) << shift;
   for (; i < groups; i += stride) {
-    // group i is fragment (i / 64) % 8 of lane i % 64 of chunk image i / 512
+    // group i is fragment (i / 64) % 8 of lane i % 64 of logical chunk image i / 512
     const size_t image = i / 512, bg = image / chunks;
-    const int c0 = static_cast<int>(image % chunks) * kAttnChunk;
+    const int lc = static_cast<int>(image % chunks), c0 = lc * kAttnChunk;
     const int b = static_cast<int>(bg / Hkv), g = static_cast<int>(bg % Hkv);
+    const int L = lens[b];
+    size_t dst = image;
+    if (table) {
+      const size_t pg = static_cast<size_t>(table[static_cast<size_t>(b) * W + (lc >> shift)]);
+      dst = ((pg * Hkv + g) << shift) + (lc & ((1 << shift) - 1));
+    }
     const int frag = static_cast<int>(i / 64) & 7, lane = static_cast<int>(i) & 63;
     const int fr = lane & 15, fq = lane >> 4;
     bf16x8 kv, vv;
@@ -342,12 +389,30 @@ __global__ __launch_bounds__(kBlock) void attn_fill_kv_kernel(
         vv[j] = static_cast<short>(attn_int_bf16(t < L ? attn_pat_v(b, g, t, d) : 0));
       }
     }
-    *reinterpret_cast<bf16x8*>(k + i * 8) = kv;
-    *reinterpret_cast<bf16x8*>(vt + i * 8) = vv;
+    const size_t at = (dst * 512 + i % 512) * 8;
+    *reinterpret_cast<bf16x8*>(k + at) = kv;
+    *reinterpret_cast<bf16x8*>(vt + at) = vv;
   }
 }
 
 // ---- host layer ----------------------------------------------------------
+
+// What the host layer of the paged payloads (payload_attn_paged.hpp) needs to
+// know of a cache format: the element, what the host entry is given, the keys
+// and elements of a chunk image, the elements of a 16-byte lane load, where an
+// element sits in the image and how the host converts one. This is the bf16
+// format; AttnCacheFp8 is in payload_attn_fp8.hpp.
+struct AttnCacheBf16 {
+  using Elem = uint16_t;
+  using Host = float;
+  static constexpr int kChunk = kAttnChunk;
+  static constexpr int kImage = kAttnChunkElems;
+  static constexpr int kLane = 8;
+
+  static int k_off(int w, int d) { return attn_k_off(w, d); }
+  static int v_off(int w, int d) { return attn_v_off(w, d); }
+  static Elem encode(float x) { return to_bf16_rne(x); }
+};
 
 // what run_attn_check and run_prefill_check return
 struct AttnCheck {
@@ -391,6 +456,14 @@ inline float attn_c2(float scale) { return scale * 1.4426950408889634f; }
 // row t of the 16 spread rows that a timed run checks, out of `rows`
 inline size_t attn_spread_row(int t, size_t rows) {
   return (static_cast<size_t>(t) * 1031 + 17) % rows;
+}
+
+// max |got - want| over n floats
+inline double attn_max_err(const float* got, const float* want, size_t n) {
+  double e = 0;
+  for (size_t i = 0; i < n; ++i)
+    note_err(e, std::fabs(static_cast<double>(got[i]) - static_cast<double>(want[i])));
+  return e;
 }
 
 // fp64 reference of one output row over its first n keys (all of them in
@@ -648,9 +721,7 @@ inline AttnCheck run_attn_check(int B, int Hq, int Hkv, int L, int splits = 0,
   attn_check_pattern(q.data(), k.data(), v.data(), want.data(), B, Hq, Hkv, L);
   attn_decode(q.data(), k.data(), v.data(), nullptr, got.data(), B, Hq, Hkv, L,
               scale, splits, device);
-  for (size_t i = 0; i < nq; ++i)
-    detail::note_err(r.max_err, std::fabs(static_cast<double>(got[i]) -
-                                          static_cast<double>(want[i])));
+  r.max_err = detail::attn_max_err(got.data(), want.data(), nq);
 
   double vmax = 0;
   for (size_t i = 0; i < nq; ++i) q[i] = detail::attn_dense(1, i, 256);
@@ -691,9 +762,10 @@ inline AttnResult run_attn(int B = 32, int Hq = 64, int Hkv = 8, int L = 4096,
   detail::attn_pattern_q(q.data(), B, Hq);
   p.upload_q_lens(q.data(), nullptr);
   const size_t groups = p.kv_elems() / 8;
-  hipLaunchKernelGGL(attn_fill_kv_kernel, dim3(grid_for(groups)), dim3(kBlock), 0, 0,
-                     p.dk.as<uint16_t>(), p.dvt.as<uint16_t>(), Hkv, L,
-                     static_cast<int>(p.Lp), groups);
+  hipLaunchKernelGGL(attn_paged_fill_kernel, dim3(grid_for(groups)), dim3(kBlock), 0, 0,
+                     p.dk.as<uint16_t>(), p.dvt.as<uint16_t>(),
+                     static_cast<const int*>(nullptr), p.dlens.as<const int>(), Hkv,
+                     static_cast<int>(p.Lp / kAttnChunk), 0, groups);
   HIP_CHECK(hipGetLastError());
   const float scale = detail::attn_default_scale();
   const float ms = detail::time_launches(iters, [&p, scale] { p.launch(scale); });
@@ -709,9 +781,7 @@ inline AttnResult run_attn(int B = 32, int Hq = 64, int Hkv = 8, int L = 4096,
                         kAttnD * sizeof(float), hipMemcpyDeviceToHost));
     detail::attn_pattern_row(want.data(), static_cast<int>(row / Hq),
                              static_cast<int>(row % Hq), p.G, L);
-    for (int d = 0; d < kAttnD; ++d)
-      detail::note_err(r.max_err, std::fabs(static_cast<double>(got[d]) -
-                                            static_cast<double>(want[d])));
+    detail::note_err(r.max_err, detail::attn_max_err(got.data(), want.data(), kAttnD));
   }
   return r;
 }

@@ -57,8 +57,8 @@
 //                MFMA). Chunks at and beyond ceil(len[b] / 64) are never read,
 //                nor are pages that no entry below a length names.
 //
-// Included by payload_core.hpp after payload_attn_paged.hpp, whose plan,
-// combine kernel, problem struct and host helpers it uses, and after
+// Included by payload_core.hpp after payload_attn_paged.hpp, whose plan, combine
+// kernel, problem struct, check case and timed run it uses, and after
 // payload_mxgemm.hpp (to_e4m3_sat, from_e4m3).
 
 #pragma once
@@ -115,10 +115,27 @@ __device__ __forceinline__ bf16x8 attn8_widen(unsigned lo, unsigned hi) {
   return __builtin_bit_cast(bf16x8, w);
 }
 
+// The e4m3 cache format as the host layer of payload_attn_paged.hpp sees it: 64
+// keys per chunk, one byte per element, codes taken as they are.
+struct AttnCacheFp8 {
+  using Elem = uint8_t;
+  using Host = uint8_t;  // the host entry is given codes
+  static constexpr int kChunk = kAttn8Chunk;
+  static constexpr int kImage = kAttn8ChunkBytes;
+  static constexpr int kLane = 16;
+
+  static int k_off(int w, int d) { return attn8_k_off(w, d); }
+  static int v_off(int w, int d) { return attn8_v_off(w, d); }
+  static Elem encode(uint8_t code) { return code; }
+};
+
 // q: [B][Hkv][16][128] bf16, rows G .. 15 zero. kp, vp: the pool's chunk images
 // of e4m3 codes. k_scale, v_scale: [Hkv]. table: [B][W]. shift = log2(page /
 // 64). items, seq, nitems: the plan in 64-key chunks. Partials and grid as in
-// attn_paged_decode_kernel.
+// attn_paged_decode_kernel, whose walk and chunk step this kernel repeats at 16
+// keys per lane. One kernel templated over both formats computed the same bits
+// but was 0.4 % slower on the ragged batch in this format
+// (profiles/paged8_probe.md), so this body stays.
 __global__ __launch_bounds__(kBlock) void attn_paged_decode_fp8_kernel(
     const uint16_t* __restrict__ q, const uint8_t* __restrict__ kp,
     const uint8_t* __restrict__ vp, const float* __restrict__ k_scale,
@@ -342,18 +359,17 @@ namespace detail {
 
 inline bool attn8_nan_code(uint8_t c) { return (c & 0x7F) == 0x7F; }
 
-// The paged problem with one byte per cache element, 64-key chunks and scales.
-struct AttnPaged8Problem : AttnPagedProblem {
+// The paged problem over the e4m3 cache: its limits and its scales.
+struct AttnPaged8Problem : AttnPagedProblem<AttnCacheFp8> {
   DeviceBuffer dks, dvs;
 
   AttnPaged8Problem(int b, int hq, int hkv, int pg, int w, int p, int workgroups, int dev)
       : AttnPagedProblem(b, hq, hkv, pg, w, p, workgroups, dev) {
     attn_paged_fp8_shape(b, hq, hkv, pg, w, p, workgroups);
-    shift = __builtin_ctz(pg / kAttn8Chunk);
   }
 
   void alloc() {
-    AttnPagedProblem::alloc(sizeof(uint8_t));
+    AttnPagedProblem::alloc();
     dks.alloc(static_cast<size_t>(Hkv) * sizeof(float));
     dvs.alloc(static_cast<size_t>(Hkv) * sizeof(float));
   }
@@ -365,41 +381,17 @@ struct AttnPaged8Problem : AttnPagedProblem {
                         hipMemcpyHostToDevice));
   }
 
-  // k, v (P, Hkv, page, 128) codes -> the pool's chunk images, every page of it
-  void upload_pool(const uint8_t* k, const uint8_t* v) {
-    std::vector<uint8_t> hk(pool_elems()), hv(pool_elems());
-    const size_t heads = static_cast<size_t>(P) * Hkv;
-    for (size_t pgh = 0; pgh < heads; ++pgh)
-      for (int t = 0; t < page; ++t) {
-        const size_t src = (pgh * page + t) * kAttnD;
-        const size_t image = ((pgh << shift) + t / kAttn8Chunk) * kAttn8ChunkBytes;
-        const int w = t % kAttn8Chunk;
-        for (int d = 0; d < kAttnD; ++d) {
-          hk[image + attn8_k_off(w, d)] = k[src + d];
-          hv[image + attn8_v_off(w, d)] = v[src + d];
-        }
-      }
-    HIP_CHECK(hipMemcpy(dk.p, hk.data(), hk.size(), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dvt.p, hv.data(), hv.size(), hipMemcpyHostToDevice));
-  }
-
   // plan (64-key chunks) + decode + combine
   void launch(float scale) const {
-    hipLaunchKernelGGL(attn_paged_plan_kernel, dim3(1), dim3(kBlock), 0, 0,
-                       dlens.as<const int>(), B, L, target, ditems.as<int4>(),
-                       dseq.as<int2>(), dnitems.as<int>(), kAttn8Chunk);
-    dim3 grid(static_cast<unsigned>(Hkv), static_cast<unsigned>(max_items()));
-    hipLaunchKernelGGL(attn_paged_decode_fp8_kernel, grid, dim3(kBlock), 0, 0,
+    plan();
+    hipLaunchKernelGGL(attn_paged_decode_fp8_kernel, grid(), dim3(kBlock), 0, 0,
                        dq.as<const uint16_t>(), dk.as<const uint8_t>(),
                        dvt.as<const uint8_t>(), dks.as<const float>(),
                        dvs.as<const float>(), dtable.as<const int>(),
                        dlens.as<const int>(), ditems.as<const int4>(),
                        dnitems.as<const int>(), dseq.as<const int2>(), dpm.as<float>(),
-                       dpl.as<float>(), dpo.as<float>(), G, W, shift, L, attn_c2(scale));
-    hipLaunchKernelGGL(attn_paged_combine_kernel, dim3(static_cast<unsigned>(rows())),
-                       dim3(kAttnD), 0, 0, dpm.as<const float>(), dpl.as<const float>(),
-                       dpo.as<const float>(), dseq.as<const int2>(), dout.as<float>(),
-                       Hq);
+                       dpl.as<float>(), dpo.as<float>(), G, W, shift(), L, attn_c2(scale));
+    combine();
   }
 };
 
@@ -426,55 +418,28 @@ inline void attn_paged_decode_fp8(const float* q, const uint8_t* k_codes,
   for (size_t i = 0, n = p.rows() * kAttnD; i < n; ++i)
     if (!std::isfinite(q[i]))
       throw std::invalid_argument("attn_paged_fp8: q has a non-finite element");
-  for (int b = 0; b < B; ++b) {
-    const int read = static_cast<int>(detail::round_up(lens[b], kAttn8Chunk));
-    for (int g = 0; g < Hkv; ++g)
-      for (int t = 0; t < read; ++t) {
-        const size_t pg = static_cast<size_t>(table[static_cast<size_t>(b) * W + t / page]);
-        const size_t at = ((pg * Hkv + g) * page + t % page) * kAttnD;
-        for (int d = 0; d < kAttnD; ++d)
-          if (detail::attn8_nan_code(k_codes[at + d]) ||
-              detail::attn8_nan_code(v_codes[at + d]))
-            throw std::invalid_argument(
-                "attn_paged_fp8: k or v has a NaN code in a chunk that is read");
-      }
-  }
+  detail::attn_paged_check_read(
+      k_codes, v_codes, table, lens, B, Hkv, page, W, kAttn8Chunk, detail::attn8_nan_code,
+      "attn_paged_fp8: k or v has a NaN code in a chunk that is read");
   p.alloc();
   p.upload_q_table(q, table, lens);
   p.upload_scales(k_scale, v_scale);
   p.upload_pool(k_codes, v_codes);
   p.launch(scale);
   HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipMemcpy(o, p.dout.p, p.rows() * kAttnD * sizeof(float),
-                      hipMemcpyDeviceToHost));
+  p.download(o);
 }
 
 namespace detail {
 
-// One paged fp8 problem of the checks: lengths, a scrambled table with -1 above
-// a length, a pool with B spare pages that is all NaN codes until scatter()
-// writes what will be read, 448 (0x7E) at the stale keys of a read chunk.
-struct Attn8Case {
-  int B, Hq, Hkv, G, page, W, P, Lmax, workgroups, device;
-  std::vector<int> lens, table;
+// The paged case of the fp8 checks: the pool is all NaN codes but for what will
+// be read, with 448 (0x7E) at the stale keys of a read chunk.
+struct Attn8Case : AttnPagedCase {
   std::vector<float> ks, vs;
 
   Attn8Case(int b, int hq, int hkv, int pg, std::vector<int> lengths, int wg, int dev)
-      : B(b), Hq(hq), Hkv(hkv), page(pg), workgroups(wg), device(dev),
-        lens(std::move(lengths)), ks(hkv), vs(hkv) {
-    Lmax = *std::max_element(lens.begin(), lens.end());
-    W = (Lmax + page - 1) / page;
-    const long long Pll = static_cast<long long>(B) * W + B;
-    G = attn_paged_fp8_shape(B, Hq, Hkv, page, W, Pll, workgroups);
-    P = static_cast<int>(Pll);
-    table = attn_paged_scrambled_table(B, W, P);
-    for (int i = 0; i < B; ++i)
-      for (int w = (lens[i] + page - 1) / page; w < W; ++w)
-        table[static_cast<size_t>(i) * W + w] = -1;
-  }
+      : AttnPagedCase(b, hq, hkv, pg, std::move(lengths), wg, dev), ks(hkv), vs(hkv) {}
 
-  size_t nq() const { return static_cast<size_t>(B) * Hq * kAttnD; }
-  size_t nkv() const { return static_cast<size_t>(B) * Hkv * Lmax * kAttnD; }
   // kv head of dense element i of (B, Hkv, Lmax, 128)
   int head(size_t i) const {
     return static_cast<int>(i / (static_cast<size_t>(Lmax) * kAttnD) % Hkv);
@@ -482,33 +447,11 @@ struct Attn8Case {
 
   // dense codes (B, Hkv, Lmax, 128) -> the pool -> the kernel
   void decode(const float* q, const uint8_t* kc, const uint8_t* vc, float* got) const {
-    const size_t npool = static_cast<size_t>(P) * Hkv * page * kAttnD;
-    std::vector<uint8_t> kpool(npool, 0x7F), vpool(npool, 0x7F);
-    attn_paged_scatter<uint8_t>(kc, kpool.data(), table.data(), lens.data(), B, Hkv, Lmax,
-                                page, W, 0x7E, kAttn8Chunk);
-    attn_paged_scatter<uint8_t>(vc, vpool.data(), table.data(), lens.data(), B, Hkv, Lmax,
-                                page, W, 0x7E, kAttn8Chunk);
+    const std::vector<uint8_t> kpool = pool<uint8_t>(kc, 0x7F, 0x7E, kAttn8Chunk);
+    const std::vector<uint8_t> vpool = pool<uint8_t>(vc, 0x7F, 0x7E, kAttn8Chunk);
     attn_paged_decode_fp8(q, kpool.data(), vpool.data(), ks.data(), vs.data(),
                           table.data(), lens.data(), got, B, Hq, Hkv, page, W, P,
                           attn_default_scale(), workgroups, device);
-  }
-
-  // max |got - fp64 attention on (q, k, v)| / max |v|
-  double rel_error(const float* got, const float* q, const float* k, const float* v) const {
-    std::vector<double> w(Lmax), ref(kAttnD);
-    double max_abs = 0, vmax = 0;
-    for (size_t i = 0; i < nkv(); ++i)
-      vmax = std::max(vmax, std::fabs(static_cast<double>(v[i])));
-    for (int b = 0; b < B; ++b)
-      for (int h = 0; h < Hq; ++h) {
-        const size_t bg = static_cast<size_t>(b) * Hkv + h / G;
-        const size_t at = (static_cast<size_t>(b) * Hq + h) * kAttnD;
-        attn_ref_row(ref.data(), q + at, k + bg * Lmax * kAttnD, v + bg * Lmax * kAttnD,
-                     lens[b], static_cast<double>(attn_default_scale()), w);
-        for (int d = 0; d < kAttnD; ++d)
-          note_err(max_abs, std::fabs(static_cast<double>(got[at + d]) - ref[d]));
-      }
-    return vmax > 0 ? max_abs / vmax : max_abs;
   }
 
   // The dense hash pattern of run_attn_check (q in [-4, 4], k and v in [-1, 1])
@@ -584,9 +527,7 @@ inline AttnCheck run_attn_paged_fp8_check(int B, int Hq, int Hkv, int L, int pag
   }
   AttnCheck r;
   c.decode(q.data(), kc.data(), vc.data(), got.data());
-  for (size_t i = 0; i < c.nq(); ++i)
-    detail::note_err(r.max_err, std::fabs(static_cast<double>(got[i]) -
-                                          static_cast<double>(want[i])));
+  r.max_err = detail::attn_max_err(got.data(), want.data(), c.nq());
   double quant_rel;
   c.dense(r.max_rel, quant_rel);
   return r;
@@ -605,55 +546,31 @@ inline AttnPaged8Result run_attn_paged_fp8(int B = 32, int Hq = 64, int Hkv = 8,
                                            int L = 4096, int page = 64, int iters = 10,
                                            bool ragged = false, int workgroups = 0,
                                            int device = 0) {
-  if (iters < 1) throw std::invalid_argument("run_attn_paged_fp8: iters must be >= 1");
-  if (L < 1 || L > (1 << 28))
-    throw std::invalid_argument("run_attn_paged_fp8: L must be in 1 .. 2^28");
-  attn_paged_fp8_shape(B, Hq, Hkv, page, 1, 1, workgroups);
-  const int W = (L + page - 1) / page;
-  const long long Pll = static_cast<long long>(B) * W + 3;
-  attn_paged_fp8_shape(B, Hq, Hkv, page, W, Pll, workgroups);
-  const int P = static_cast<int>(Pll);
-  const std::vector<int> lens = detail::attn_paged_lens(B, L, ragged);
+  using C = AttnCacheFp8;
+  const detail::AttnPagedTimed t("run_attn_paged_fp8", attn_paged_fp8_shape, B, Hq, Hkv, L,
+                                 page, iters, ragged, workgroups);
   const float scale = detail::attn_default_scale();
   AttnPaged8Result r;
   {
-    detail::AttnPaged8Problem p(B, Hq, Hkv, page, W, P, workgroups, device);
-    std::vector<float> q(p.rows() * kAttnD), ks(Hkv), vs(Hkv);
-    detail::attn_pattern_q(q.data(), B, Hq);
-    for (int g = 0; g < Hkv; ++g) {
-      ks[g] = attn8_k_scale(g);
-      vs[g] = attn8_v_scale(g);
-    }
-    const std::vector<int> table = detail::attn_paged_scrambled_table(B, W, P);
-    p.alloc();
-    p.upload_q_table(q.data(), table.data(), lens.data());
-    p.upload_scales(ks.data(), vs.data());
-    const size_t groups = static_cast<size_t>(B) * Hkv * W * page * kAttnD / 16;
-    hipLaunchKernelGGL(attn_paged_fill_fp8_kernel, dim3(grid_for(groups)), dim3(kBlock), 0,
-                       0, p.dk.as<uint8_t>(), p.dvt.as<uint8_t>(),
-                       p.dtable.as<const int>(), p.dlens.as<const int>(), Hkv, W, p.shift,
-                       groups);
-    HIP_CHECK(hipGetLastError());
-    const double sec =
-        detail::time_launches(iters, [&p, scale] { p.launch(scale); }) * 1e-3;
-    double keys = 0;
-    for (int len : lens) keys += len;
-    r.us = sec / iters * 1e6;
-    r.steps_per_s = iters / sec;
-    r.tok_per_s = r.steps_per_s * B;
-    r.kv_gb_s = keys * Hkv * kAttnD * 2.0 * iters / sec / 1e9;
-    r.items = p.items();
-    std::vector<float> got(kAttnD), want(kAttnD);
-    for (int t = 0; t < 16; ++t) {
-      const size_t row = detail::attn_spread_row(t, p.rows());
-      HIP_CHECK(hipMemcpy(got.data(), p.dout.as<float>() + row * kAttnD,
-                          kAttnD * sizeof(float), hipMemcpyDeviceToHost));
-      const int b = static_cast<int>(row / Hq);
-      detail::attn_pattern_row(want.data(), b, static_cast<int>(row % Hq), p.G, lens[b]);
-      for (int d = 0; d < kAttnD; ++d)
-        detail::note_err(r.max_err, std::fabs(static_cast<double>(got[d]) -
-                                              static_cast<double>(want[d])));
-    }
+    detail::AttnPaged8Problem p(B, Hq, Hkv, page, t.W, t.P, workgroups, device);
+    const float ms = t.time(
+        r, p,
+        [&] {
+          std::vector<float> ks(Hkv), vs(Hkv);
+          for (int g = 0; g < Hkv; ++g) {
+            ks[g] = attn8_k_scale(g);
+            vs[g] = attn8_v_scale(g);
+          }
+          p.upload_scales(ks.data(), vs.data());
+          const size_t groups = static_cast<size_t>(B) * Hkv * t.W * page * kAttnD / C::kLane;
+          hipLaunchKernelGGL(attn_paged_fill_fp8_kernel, dim3(grid_for(groups)),
+                             dim3(kBlock), 0, 0, p.dk.as<uint8_t>(), p.dvt.as<uint8_t>(),
+                             p.dtable.as<const int>(), p.dlens.as<const int>(), Hkv, t.W,
+                             p.shift(), groups);
+        },
+        [&p, scale] { p.launch(scale); });
+    r.us = ms * 1e-3 / iters * 1e6;
+    t.report(r, ms, p.dout.as<float>(), 2 * sizeof(C::Elem));
   }
   r.bf16_us =
       1e6 / run_attn_paged(B, Hq, Hkv, L, page, iters, ragged, workgroups, device)

@@ -55,9 +55,14 @@
 // Partials of row (b, h) start at first_part[b] * Hq + h * n_b * 4, part =
 // item of the sequence * 4 + wave: a row's partials are contiguous.
 //
+// The problem struct, the check case and the timed run stand once here for
+// every cache format; payload_attn_fp8.hpp adds the e4m3 format (AttnCacheFp8)
+// to the bf16 one (AttnCacheBf16). Each format has its own decode kernel.
+//
 // Included by payload_core.hpp after payload_attn.hpp, whose helpers it uses:
-// the layout and pattern functions, attn_p_bf16, detail::attn_ref_row, the
-// dense hash pattern and kAttnRelBound.
+// the chunk step (attn_load_q, attn_load_image, attn_qk, attn_softmax_pv,
+// attn_write_partial), the fill kernel, the layout and pattern functions,
+// detail::attn_ref_row, the dense hash pattern and kAttnRelBound.
 
 #pragma once
 
@@ -172,7 +177,7 @@ __global__ __launch_bounds__(kBlock) void attn_paged_plan_kernel(
 // images. table: [B][W]. shift = log2(page / 32). Partials as described at the
 // top. grid = (Hkv, target + B): the kv head is the fast index, so that the
 // workgroups beyond the item count are the last to be dispatched and take no
-// CU from a live one. The chunk step is attn_decode_kernel's.
+// CU from a live one. The chunk step is attn_decode_kernel's (payload_attn.hpp).
 __global__ __launch_bounds__(kBlock) void attn_paged_decode_kernel(
     const uint16_t* __restrict__ q, const uint16_t* __restrict__ kp,
     const uint16_t* __restrict__ vp, const int* __restrict__ table,
@@ -200,91 +205,36 @@ __global__ __launch_bounds__(kBlock) void attn_paged_decode_kernel(
   };
 
   bf16x8 fqt[kAttnD / 32];
-  {
-    const uint16_t* qb =
-        q + ((static_cast<size_t>(b) * Hkv + g) * 16 + fr) * kAttnD + fq * 8;
-#pragma unroll
-    for (int s = 0; s < kAttnD / 32; ++s)
-      fqt[s] = *reinterpret_cast<const bf16x8*>(qb + s * 32);
-  }
+  attn_load_q(fqt, q, static_cast<size_t>(b) * Hkv + g, fr, fq);
 
   float m = -INFINITY, l = 0.f;
   f32x4 o[kAttnD / 16];
 #pragma unroll
   for (int dt = 0; dt < kAttnD / 16; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  bf16x8 fk[2][kAttnD / 32];
-  auto load_k = [&](int pg, int ch) {
-    const uint16_t* kc = kp + image(pg, ch);
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int s = 0; s < kAttnD / 32; ++s)
-        fk[t][s] = *reinterpret_cast<const bf16x8*>(kc + (t * 4 + s) * 512);
-  };
-
   // pg_v: the page of the chunk in hand (its K is in flight or here); pg_k: the
   // page of the wave's next chunk, fetched a whole chunk before its K loads
+  bf16x8 fk[8];
   int ch = it.y + wave;
   int pg_v = 0, pg_k = 0;
   if (ch < ch_end) {
     pg_v = trow[ch >> shift];
-    load_k(pg_v, ch);
+    attn_load_image(fk, kp + image(pg_v, ch));
   }
   if (ch + kAttnWaves < ch_end) pg_k = trow[(ch + kAttnWaves) >> shift];
 
   for (; ch < ch_end; ch += kAttnWaves) {  // wave-uniform
-    const int c0 = ch * kAttnChunk;
-    const uint16_t* vc = vp + image(pg_v, ch);
-    bf16x8 fv[kAttnD / 16];
-#pragma unroll
-    for (int dt = 0; dt < kAttnD / 16; ++dt)
-      fv[dt] = *reinterpret_cast<const bf16x8*>(vc + dt * 512);
-
-    f32x4 st[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int s = 0; s < kAttnD / 32; ++s)
-        st[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fk[t][s], fqt[s], st[t],
-                                                        0, 0, 0);
+    bf16x8 fv[8];
+    attn_load_image(fv, vp + image(pg_v, ch));
+    f32x4 st[2];
+    attn_qk(fk, fqt, st);
 
     const int nx = ch + kAttnWaves;
-    if (nx < ch_end) load_k(pg_k, nx);
+    if (nx < ch_end) attn_load_image(fk, kp + image(pg_k, nx));
     pg_v = pg_k;
     if (nx + kAttnWaves < ch_end) pg_k = trow[(nx + kAttnWaves) >> shift];
 
-    float sc[8];
-    float cm = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int key = c0 + 8 * fq + j;
-      sc[j] = key < len ? st[j >> 2][j & 3] * c2 : -INFINITY;
-      cm = fmaxf(cm, sc[j]);
-    }
-    cm = fmaxf(cm, __shfl_xor(cm, 16));
-    cm = fmaxf(cm, __shfl_xor(cm, 32));
-
-    const float mn = fmaxf(m, cm);
-    const float ms = mn == -INFINITY ? 0.f : mn;  // never (-inf) - (-inf)
-    const float alpha = __builtin_amdgcn_exp2f(m - ms);  // m = -inf: 0
-    m = mn;
-
-    bf16x8 fp;
-    float sum = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float p = __builtin_amdgcn_exp2f(sc[j] - ms);
-      sum += p;  // l takes the unrounded weight
-      fp[j] = attn_p_bf16(p);
-    }
-    l = l * alpha + sum;
-
-#pragma unroll
-    for (int dt = 0; dt < kAttnD / 16; ++dt) {
-      o[dt] *= alpha;
-      o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fv[dt], fp, o[dt], 0, 0, 0);
-    }
+    attn_softmax_pv(st, fv, ch * kAttnChunk, fq, len, c2, m, l, o);
   }
 
   l += __shfl_xor(l, 16);
@@ -296,13 +246,7 @@ __global__ __launch_bounds__(kBlock) void attn_paged_decode_kernel(
     const size_t part = static_cast<size_t>(sq.x) * Hq +
                         (static_cast<size_t>(g) * G + fr) * sq.y +
                         static_cast<size_t>(it.w) * kAttnWaves + wave;
-    if (fq == 0) {
-      pm[part] = m;
-      pl[part] = l;
-    }
-#pragma unroll
-    for (int dt = 0; dt < kAttnD / 16; ++dt)
-      *reinterpret_cast<f32x4*>(po + part * kAttnD + dt * 16 + fq * 4) = o[dt];
+    attn_write_partial(pm, pl, po, part, fq, m, l, o);
   }
 }
 
@@ -330,56 +274,6 @@ __global__ __launch_bounds__(kAttnD) void attn_paged_combine_kernel(
     acc += w * o[static_cast<size_t>(i) * kAttnD];
   }
   out[row * kAttnD + d] = acc / ls;  // the only division, and a true one
-}
-
-// Device-side fill of the selection pattern at the lengths lens[b], one
-// fragment of each tensor per thread and step, over the logical chunks of all
-// W pages of every sequence; keys at and beyond lens[b] are zero. The image of
-// logical chunk lc of (b, g) is found through the table, or, with table null,
-// at (b * Hkv + g) * chunks + lc: the contiguous layout of payload_attn.hpp.
-__global__ __launch_bounds__(kBlock) void attn_paged_fill_kernel(
-    uint16_t* __restrict__ k, uint16_t* __restrict__ vt, const int* __restrict__ table,
-    const int* __restrict__ lens, int Hkv, int W, int shift,
-    size_t groups) {  // groups = B Hkv (W << shift) 4096 / 8, per tensor
-  size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
-  const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
-  const size_t chunks = static_cast<size_t>(W) << shift;
-  for (; i < groups; i += stride) {
-    const size_t image = i / 512, bg = image / chunks;
-    const int lc = static_cast<int>(image % chunks), c0 = lc * kAttnChunk;
-    const int b = static_cast<int>(bg / Hkv), g = static_cast<int>(bg % Hkv);
-    const int L = lens[b];
-    size_t dst = image;
-    if (table) {
-      const size_t pg = static_cast<size_t>(table[static_cast<size_t>(b) * W + (lc >> shift)]);
-      dst = ((pg * Hkv + g) << shift) + (lc & ((1 << shift) - 1));
-    }
-    const int frag = static_cast<int>(i / 64) & 7, lane = static_cast<int>(i) & 63;
-    const int fr = lane & 15, fq = lane >> 4;
-    bf16x8 kv, vv;
-    {
-      const int t = c0 + 8 * (fr >> 2) + 4 * (frag >> 2) + (fr & 3);
-      const int d0 = 32 * (frag & 3) + 8 * fq;
-      const bool sel = t < L && attn_selected(b, g, t, L);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        int val = 0;
-        if (t < L && !sel) val = attn_pat_k_off(g, t, d0 + j);
-        kv[j] = static_cast<short>(attn_int_bf16(val));
-      }
-    }
-    {
-      const int d = 16 * frag + fr;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int t = c0 + 8 * fq + j;
-        vv[j] = static_cast<short>(attn_int_bf16(t < L ? attn_pat_v(b, g, t, d) : 0));
-      }
-    }
-    const size_t at = (dst * 512 + i % 512) * 8;
-    *reinterpret_cast<bf16x8*>(k + at) = kv;
-    *reinterpret_cast<bf16x8*>(vt + at) = vv;
-  }
 }
 
 // ---- host layer ----------------------------------------------------------
@@ -436,20 +330,24 @@ inline std::vector<int> attn_paged_scrambled_table(int B, int W, int P) {
   return table;
 }
 
-// Shape, device buffers and launch of one paged problem.
+// Shape and device buffers of one paged problem over a cache of format C
+// (AttnCacheBf16, AttnCacheFp8), and of a step's three launches the two that do
+// not depend on the format; a format's problem adds launch() with its decode
+// kernel between them.
+template <class C>
 struct AttnPagedProblem : AttnShape {
-  int page, W, P, shift, target;
+  int page, W, P, target;
   DeviceBuffer dq, dk, dvt, dtable, dlens, ditems, dseq, dnitems, dpm, dpl, dpo, dout;
 
   // L is the longest a sequence may be, W page; the shape is checked before
   // that product is formed
   AttnPagedProblem(int b, int hq, int hkv, int pg, int w, int p, int workgroups, int dev)
       : AttnShape{b, hq, hkv, 0, attn_paged_shape(b, hq, hkv, pg, w, p, workgroups), dev},
-        page(pg), W(w), P(p), shift(pg == 32 ? 0 : pg == 64 ? 1 : pg == 128 ? 2 : 3),
-        target(workgroups) {
+        page(pg), W(w), P(p), target(workgroups) {
     L = w * pg;
   }
 
+  int shift() const { return __builtin_ctz(page / C::kChunk); }  // chunks of a page
   size_t pool_elems() const {
     return static_cast<size_t>(P) * Hkv * page * kAttnD;
   }
@@ -458,8 +356,7 @@ struct AttnPagedProblem : AttnShape {
 
   // workgroups = 0: items for half the visible CUs, the count that
   // profiles/attn_probe.md found best for the contiguous kernel
-  // kv_bytes: per cache element, 2 for bf16
-  void alloc(size_t kv_bytes = sizeof(uint16_t)) {
+  void alloc() {
     HIP_CHECK(hipSetDevice(device));
     if (target == 0) {
       int cus = 0;
@@ -469,8 +366,8 @@ struct AttnPagedProblem : AttnShape {
     }
     const size_t parts = static_cast<size_t>(max_items()) * kAttnWaves * Hq;
     dq.alloc(static_cast<size_t>(B) * Hkv * 16 * kAttnD * sizeof(uint16_t));
-    dk.alloc(pool_elems() * kv_bytes);
-    dvt.alloc(pool_elems() * kv_bytes);
+    dk.alloc(pool_elems() * sizeof(typename C::Elem));
+    dvt.alloc(pool_elems() * sizeof(typename C::Elem));
     dtable.alloc(static_cast<size_t>(B) * W * sizeof(int));
     dlens.alloc(static_cast<size_t>(B) * sizeof(int));
     ditems.alloc(static_cast<size_t>(max_items()) * sizeof(int4));
@@ -499,49 +396,68 @@ struct AttnPagedProblem : AttnShape {
                         hipMemcpyHostToDevice));
   }
 
-  // k_pages, v_pages (P, Hkv, page, 128) float -> the pool's chunk images, every
-  // page of it, referenced or not
-  void upload_pool(const float* k, const float* v) {
-    std::vector<uint16_t> hk(pool_elems()), hvt(pool_elems());
+  // k, v (P, Hkv, page, 128) in plain key-major order -> the pool's chunk
+  // images, every page of it, referenced or not
+  void upload_pool(const typename C::Host* k, const typename C::Host* v) {
+    std::vector<typename C::Elem> hk(pool_elems()), hvt(pool_elems());
     const size_t heads = static_cast<size_t>(P) * Hkv;
     for (size_t pgh = 0; pgh < heads; ++pgh)
       for (int t = 0; t < page; ++t) {
         const size_t src = (pgh * page + t) * kAttnD;
-        const size_t image = ((pgh << shift) + t / kAttnChunk) * kAttnChunkElems;
-        const int w = t % kAttnChunk;
+        const size_t image = ((pgh << shift()) + t / C::kChunk) * C::kImage;
+        const int w = t % C::kChunk;
         for (int d = 0; d < kAttnD; ++d) {
-          hk[image + attn_k_off(w, d)] = to_bf16_rne(k[src + d]);
-          hvt[image + attn_v_off(w, d)] = to_bf16_rne(v[src + d]);
+          hk[image + C::k_off(w, d)] = C::encode(k[src + d]);
+          hvt[image + C::v_off(w, d)] = C::encode(v[src + d]);
         }
       }
-    HIP_CHECK(hipMemcpy(dk.p, hk.data(), hk.size() * sizeof(uint16_t),
+    HIP_CHECK(hipMemcpy(dk.p, hk.data(), hk.size() * sizeof(typename C::Elem),
                         hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dvt.p, hvt.data(), hvt.size() * sizeof(uint16_t),
+    HIP_CHECK(hipMemcpy(dvt.p, hvt.data(), hvt.size() * sizeof(typename C::Elem),
                         hipMemcpyHostToDevice));
   }
 
-  // plan + decode + combine
-  void launch(float scale) const {
+  // the plan in chunks of C::kChunk keys, the decode kernel's grid, the combine
+  void plan() const {
     hipLaunchKernelGGL(attn_paged_plan_kernel, dim3(1), dim3(kBlock), 0, 0,
                        dlens.as<const int>(), B, L, target, ditems.as<int4>(),
-                       dseq.as<int2>(), dnitems.as<int>());
-    dim3 grid(static_cast<unsigned>(Hkv), static_cast<unsigned>(max_items()));
-    hipLaunchKernelGGL(attn_paged_decode_kernel, grid, dim3(kBlock), 0, 0,
-                       dq.as<const uint16_t>(), dk.as<const uint16_t>(),
-                       dvt.as<const uint16_t>(), dtable.as<const int>(),
-                       dlens.as<const int>(), ditems.as<const int4>(),
-                       dnitems.as<const int>(), dseq.as<const int2>(), dpm.as<float>(),
-                       dpl.as<float>(), dpo.as<float>(), G, W, shift, L, attn_c2(scale));
+                       dseq.as<int2>(), dnitems.as<int>(), C::kChunk);
+  }
+  dim3 grid() const {
+    return dim3(static_cast<unsigned>(Hkv), static_cast<unsigned>(max_items()));
+  }
+  void combine() const {
     hipLaunchKernelGGL(attn_paged_combine_kernel, dim3(static_cast<unsigned>(rows())),
                        dim3(kAttnD), 0, 0, dpm.as<const float>(), dpl.as<const float>(),
                        dpo.as<const float>(), dseq.as<const int2>(), dout.as<float>(),
                        Hq);
+  }
+  void download(float* o) const {
+    HIP_CHECK(hipMemcpy(o, dout.p, rows() * kAttnD * sizeof(float),
+                        hipMemcpyDeviceToHost));
   }
 
   int items() const {
     int n = 0;
     HIP_CHECK(hipMemcpy(&n, dnitems.p, sizeof(int), hipMemcpyDeviceToHost));
     return n;
+  }
+};
+
+// the paged problem over the bf16 cache
+struct AttnPagedBf16Problem : AttnPagedProblem<AttnCacheBf16> {
+  using AttnPagedProblem::AttnPagedProblem;
+
+  // plan + decode + combine
+  void launch(float scale) const {
+    plan();
+    hipLaunchKernelGGL(attn_paged_decode_kernel, grid(), dim3(kBlock), 0, 0,
+                       dq.as<const uint16_t>(), dk.as<const uint16_t>(),
+                       dvt.as<const uint16_t>(), dtable.as<const int>(),
+                       dlens.as<const int>(), ditems.as<const int4>(),
+                       dnitems.as<const int>(), dseq.as<const int2>(), dpm.as<float>(),
+                       dpl.as<float>(), dpo.as<float>(), G, W, shift(), L, attn_c2(scale));
+    combine();
   }
 };
 
@@ -575,6 +491,137 @@ inline void attn_paged_scatter(const T* dense, T* pool, const int* table,
   }
 }
 
+// std::invalid_argument(msg) where bad(k) or bad(v) at an element of a key of a
+// chunk (of `chunk` keys) that will be read; the pools are (P, Hkv, page, 128)
+template <class T, class Bad>
+inline void attn_paged_check_read(const T* k, const T* v, const int* table, const int* lens,
+                                  int B, int Hkv, int page, int W, int chunk, Bad bad,
+                                  const char* msg) {
+  for (int b = 0; b < B; ++b) {
+    const int read = static_cast<int>(round_up(lens[b], chunk));
+    for (int g = 0; g < Hkv; ++g)
+      for (int t = 0; t < read; ++t) {
+        const size_t pg = static_cast<size_t>(table[static_cast<size_t>(b) * W + t / page]);
+        const size_t at = ((pg * Hkv + g) * page + t % page) * kAttnD;
+        for (int d = 0; d < kAttnD; ++d)
+          if (bad(k[at + d]) || bad(v[at + d])) throw std::invalid_argument(msg);
+      }
+  }
+}
+
+// One paged problem of the checks of either format: lengths, W pages for the
+// longest, a scrambled table with -1 above a length, and a pool with B spare
+// pages. The page size has been checked.
+struct AttnPagedCase {
+  int B, Hq, Hkv, G, page, W, P, Lmax, workgroups, device;
+  std::vector<int> lens, table;
+
+  AttnPagedCase(int b, int hq, int hkv, int pg, std::vector<int> lengths, int wg, int dev)
+      : B(b), Hq(hq), Hkv(hkv), page(pg), workgroups(wg), device(dev),
+        lens(std::move(lengths)) {
+    Lmax = *std::max_element(lens.begin(), lens.end());
+    W = (Lmax + page - 1) / page;
+    const long long Pll = static_cast<long long>(B) * W + B;
+    G = attn_paged_shape(B, Hq, Hkv, page, W, Pll, workgroups);
+    P = static_cast<int>(Pll);
+    table = attn_paged_scrambled_table(B, W, P);
+    for (int i = 0; i < B; ++i)
+      for (int w = (lens[i] + page - 1) / page; w < W; ++w)
+        table[static_cast<size_t>(i) * W + w] = -1;
+  }
+
+  size_t nq() const { return static_cast<size_t>(B) * Hq * kAttnD; }
+  size_t nkv() const { return static_cast<size_t>(B) * Hkv * Lmax * kAttnD; }
+
+  // dense (B, Hkv, Lmax, 128) -> a pool that is all `poison` but for what will
+  // be read (in chunks of `chunk` keys), with `stale` at the stale keys of that
+  template <class T>
+  std::vector<T> pool(const T* dense, T poison, T stale, int chunk) const {
+    std::vector<T> pl(static_cast<size_t>(P) * Hkv * page * kAttnD, poison);
+    attn_paged_scatter(dense, pl.data(), table.data(), lens.data(), B, Hkv, Lmax, page, W,
+                       stale, chunk);
+    return pl;
+  }
+
+  // max |got - fp64 attention on (q, k, v)| / max |v|
+  double rel_error(const float* got, const float* q, const float* k, const float* v) const {
+    std::vector<double> w(Lmax), ref(kAttnD);
+    double max_abs = 0, vmax = 0;
+    for (size_t i = 0; i < nkv(); ++i)
+      vmax = std::max(vmax, std::fabs(static_cast<double>(v[i])));
+    for (int b = 0; b < B; ++b)
+      for (int h = 0; h < Hq; ++h) {
+        const size_t bg = static_cast<size_t>(b) * Hkv + h / G;
+        const size_t at = (static_cast<size_t>(b) * Hq + h) * kAttnD;
+        attn_ref_row(ref.data(), q + at, k + bg * Lmax * kAttnD, v + bg * Lmax * kAttnD,
+                     lens[b], static_cast<double>(attn_default_scale()), w);
+        for (int d = 0; d < kAttnD; ++d)
+          note_err(max_abs, std::fabs(static_cast<double>(got[at + d]) - ref[d]));
+      }
+    return vmax > 0 ? max_abs / vmax : max_abs;
+  }
+};
+
+// What the timed runs of both formats are given and derive: the checked ranges
+// (`who` heads the messages, `shape` is the format's limits), W = ceil(L / page)
+// pages per sequence, a pool of P = B W + 3, the lengths and the pattern's q.
+struct AttnPagedTimed {
+  int B, Hq, Hkv, iters, W, P;
+  std::vector<int> lens;
+  std::vector<float> q;
+
+  template <class Shape>
+  AttnPagedTimed(const std::string& who, Shape shape, int b, int hq, int hkv, int L,
+                 int page, int it, bool ragged, int workgroups)
+      : B(b), Hq(hq), Hkv(hkv), iters(it) {
+    if (iters < 1) throw std::invalid_argument(who + ": iters must be >= 1");
+    if (L < 1 || L > (1 << 28)) throw std::invalid_argument(who + ": L must be in 1 .. 2^28");
+    shape(B, Hq, Hkv, page, 1, 1, workgroups);
+    W = (L + page - 1) / page;
+    const long long Pll = static_cast<long long>(B) * W + 3;
+    shape(B, Hq, Hkv, page, W, Pll, workgroups);
+    P = static_cast<int>(Pll);
+    lens = attn_paged_lens(B, L, ragged);
+    q.resize(static_cast<size_t>(B) * Hq * kAttnD);
+    attn_pattern_q(q.data(), B, Hq);
+  }
+
+  // the rates of `iters` launches that took ms and read kv_bytes per cache
+  // element (K and V), and the 16 spread rows of the output at dout, exactly
+  void report(AttnResult& r, float ms, const float* dout, double kv_bytes) const {
+    const double sec = ms * 1e-3;
+    double keys = 0;
+    for (int len : lens) keys += len;
+    r.steps_per_s = iters / sec;
+    r.tok_per_s = r.steps_per_s * B;
+    r.kv_gb_s = keys * Hkv * kAttnD * kv_bytes * iters / sec / 1e9;
+    std::vector<float> got(kAttnD), want(kAttnD);
+    for (int t = 0; t < 16; ++t) {
+      const size_t row = attn_spread_row(t, static_cast<size_t>(B) * Hq);
+      HIP_CHECK(hipMemcpy(got.data(), dout + row * kAttnD, kAttnD * sizeof(float),
+                          hipMemcpyDeviceToHost));
+      const int b = static_cast<int>(row / Hq);
+      attn_pattern_row(want.data(), b, static_cast<int>(row % Hq), Hq / Hkv, lens[b]);
+      note_err(r.max_err, attn_max_err(got.data(), want.data(), kAttnD));
+    }
+  }
+
+  // The paged problem p under a fixed scrambled table: `fill` writes the pool
+  // (and what else the format needs) on the device, `launch` is timed. Returns
+  // the milliseconds that report() takes, with the item count in r.
+  template <class Problem, class Fill, class Launch>
+  float time(AttnPagedResult& r, Problem& p, Fill fill, Launch launch) const {
+    const std::vector<int> table = attn_paged_scrambled_table(B, W, P);
+    p.alloc();
+    p.upload_q_table(q.data(), table.data(), lens.data());
+    fill();
+    HIP_CHECK(hipGetLastError());
+    const float ms = time_launches(iters, launch);
+    r.items = p.items();
+    return ms;
+  }
+};
+
 }  // namespace detail
 
 // General entry. q (B, Hq, 128), k_pages and v_pages (P, Hkv, page, 128), o (B,
@@ -586,40 +633,31 @@ inline void attn_paged_decode(const float* q, const float* k_pages, const float*
                               const int* table, const int* lens, float* o, int B, int Hq,
                               int Hkv, int page, int W, int P, float scale,
                               int workgroups = 0, int device = 0) {
-  detail::AttnPagedProblem p(B, Hq, Hkv, page, W, P, workgroups, device);
+  detail::AttnPagedBf16Problem p(B, Hq, Hkv, page, W, P, workgroups, device);
   detail::attn_paged_check_table(table, lens, B, page, W, P);
   for (size_t i = 0, n = p.rows() * kAttnD; i < n; ++i)
     if (!std::isfinite(q[i]))
       throw std::invalid_argument("attn_paged: q has a non-finite element");
-  for (int b = 0; b < B; ++b) {
-    const int read = static_cast<int>(detail::round_up(lens[b], kAttnChunk));
-    for (int g = 0; g < Hkv; ++g)
-      for (int t = 0; t < read; ++t) {
-        const size_t pg = static_cast<size_t>(table[static_cast<size_t>(b) * W + t / page]);
-        const size_t at = ((pg * Hkv + g) * page + t % page) * kAttnD;
-        for (int d = 0; d < kAttnD; ++d)
-          if (!std::isfinite(k_pages[at + d]) || !std::isfinite(v_pages[at + d]))
-            throw std::invalid_argument(
-                "attn_paged: k or v has a non-finite element in a chunk that is read");
-      }
-  }
+  detail::attn_paged_check_read(
+      k_pages, v_pages, table, lens, B, Hkv, page, W, kAttnChunk,
+      [](float x) { return !std::isfinite(x); },
+      "attn_paged: k or v has a non-finite element in a chunk that is read");
   p.alloc();
   p.upload_q_table(q, table, lens);
   p.upload_pool(k_pages, v_pages);
   p.launch(scale);
   HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipMemcpy(o, p.dout.p, p.rows() * kAttnD * sizeof(float),
-                      hipMemcpyDeviceToHost));
+  p.download(o);
 }
 
 // Self-check on ragged lengths derived from L, sequence b taking entry b % 4 of
 // {L, 1, the largest multiple of 32 up to max(32, L / 2), max(1, L / page) page
 // + 1}: from B = 4 on the batch holds a single key, a whole number of chunks
-// and one key past a page boundary. The pool has B more pages than the table
-// names, all NaN; the table is scrambled and holds -1 above a sequence's
-// length; stale keys of a read chunk hold 1e30 in K and V. (a) the selection
-// pattern against its closed form: max_err, expect exactly 0. (b) the dense
-// hash pattern of run_attn_check against fp64: max_rel <= 2^-8, the bound
+// and one key past a page boundary. Pool and table are detail::AttnPagedCase's:
+// B more pages than the table names, all NaN; a scrambled table with -1 above a
+// sequence's length; stale keys of a read chunk hold 1e30 in K and V. (a) the
+// selection pattern against its closed form: max_err, expect exactly 0. (b) the
+// dense hash pattern of run_attn_check against fp64: max_rel <= 2^-8, the bound
 // derived there, which does not depend on how the keys are split.
 inline AttnCheck run_attn_paged_check(int B, int Hq, int Hkv, int L, int page,
                                       int workgroups = 0, int device = 0) {
@@ -627,62 +665,31 @@ inline AttnCheck run_attn_paged_check(int B, int Hq, int Hkv, int L, int page,
     throw std::invalid_argument("attn_paged: L must be in 1 .. 2^24");
   attn_paged_shape(B, Hq, Hkv, page, 1, 1, workgroups);  // page before it divides
   const int rule[4] = {L, 1, std::max(32, L / 2) / 32 * 32, std::max(1, L / page) * page + 1};
-  const int Lmax = *std::max_element(rule, rule + 4);
-  const int W = (Lmax + page - 1) / page;
-  const long long Pll = static_cast<long long>(B) * W + B;
-  const int G = attn_paged_shape(B, Hq, Hkv, page, W, Pll, workgroups);
-  const int P = static_cast<int>(Pll);
   std::vector<int> lens(B);
   for (int b = 0; b < B; ++b) lens[b] = rule[b % 4];
-  std::vector<int> table = detail::attn_paged_scrambled_table(B, W, P);
-  for (int b = 0; b < B; ++b)
-    for (int w = (lens[b] + page - 1) / page; w < W; ++w)
-      table[static_cast<size_t>(b) * W + w] = -1;
+  const detail::AttnPagedCase c(B, Hq, Hkv, page, lens, workgroups, device);
 
-  const size_t nq = static_cast<size_t>(B) * Hq * kAttnD;
-  const size_t nkv = static_cast<size_t>(B) * Hkv * Lmax * kAttnD;
-  const size_t npool = static_cast<size_t>(P) * Hkv * page * kAttnD;
-  const float scale = detail::attn_default_scale();
-  std::vector<float> q(nq), k(nkv), v(nkv), want(nq), got(nq);
-  std::vector<float> kpool(npool, NAN), vpool(npool, NAN);
-  AttnCheck r;
+  std::vector<float> q(c.nq()), k(c.nkv()), v(c.nkv()), want(c.nq()), got(c.nq());
   auto decode = [&] {
-    detail::attn_paged_scatter(k.data(), kpool.data(), table.data(), lens.data(), B, Hkv,
-                               Lmax, page, W, 1e30f);
-    detail::attn_paged_scatter(v.data(), vpool.data(), table.data(), lens.data(), B, Hkv,
-                               Lmax, page, W, 1e30f);
-    attn_paged_decode(q.data(), kpool.data(), vpool.data(), table.data(), lens.data(),
-                      got.data(), B, Hq, Hkv, page, W, P, scale, workgroups, device);
+    const std::vector<float> kpool = c.pool(k.data(), NAN, 1e30f, kAttnChunk);
+    const std::vector<float> vpool = c.pool(v.data(), NAN, 1e30f, kAttnChunk);
+    attn_paged_decode(q.data(), kpool.data(), vpool.data(), c.table.data(), lens.data(),
+                      got.data(), B, Hq, Hkv, page, c.W, c.P, detail::attn_default_scale(),
+                      workgroups, device);
   };
-
-  attn_check_pattern(q.data(), k.data(), v.data(), want.data(), B, Hq, Hkv, Lmax,
+  AttnCheck r;
+  attn_check_pattern(q.data(), k.data(), v.data(), want.data(), B, Hq, Hkv, c.Lmax,
                      lens.data());
   decode();
-  for (size_t i = 0; i < nq; ++i)
-    detail::note_err(r.max_err, std::fabs(static_cast<double>(got[i]) -
-                                          static_cast<double>(want[i])));
+  r.max_err = detail::attn_max_err(got.data(), want.data(), c.nq());
 
-  double vmax = 0;
-  for (size_t i = 0; i < nq; ++i) q[i] = detail::attn_dense(1, i, 256);
-  for (size_t i = 0; i < nkv; ++i) {
+  for (size_t i = 0; i < c.nq(); ++i) q[i] = detail::attn_dense(1, i, 256);
+  for (size_t i = 0; i < c.nkv(); ++i) {
     k[i] = detail::attn_dense(2, i, 64);
     v[i] = detail::attn_dense(3, i, 64);
-    vmax = std::max(vmax, std::fabs(static_cast<double>(v[i])));
   }
   decode();
-  std::vector<double> w(Lmax), ref(kAttnD);
-  double max_abs = 0;
-  for (int b = 0; b < B; ++b)
-    for (int h = 0; h < Hq; ++h) {
-      const size_t bg = static_cast<size_t>(b) * Hkv + h / G;
-      const size_t at = (static_cast<size_t>(b) * Hq + h) * kAttnD;
-      detail::attn_ref_row(ref.data(), q.data() + at, k.data() + bg * Lmax * kAttnD,
-                           v.data() + bg * Lmax * kAttnD, lens[b],
-                           static_cast<double>(scale), w);
-      for (int d = 0; d < kAttnD; ++d)
-        detail::note_err(max_abs, std::fabs(static_cast<double>(got[at + d]) - ref[d]));
-    }
-  r.max_rel = vmax > 0 ? max_abs / vmax : max_abs;
+  r.max_rel = c.rel_error(got.data(), q.data(), k.data(), v.data());
   return r;
 }
 
@@ -698,70 +705,35 @@ inline AttnPagedResult run_attn_paged(int B = 32, int Hq = 64, int Hkv = 8, int 
                                       int page = 64, int iters = 10, bool ragged = false,
                                       int workgroups = 0, int device = 0,
                                       bool contiguous = false) {
-  if (iters < 1) throw std::invalid_argument("run_attn_paged: iters must be >= 1");
-  if (L < 1 || L > (1 << 28))
-    throw std::invalid_argument("run_attn_paged: L must be in 1 .. 2^28");
-  attn_paged_shape(B, Hq, Hkv, page, 1, 1, workgroups);
-  const int W = (L + page - 1) / page;
-  const long long Pll = static_cast<long long>(B) * W + 3;
-  attn_paged_shape(B, Hq, Hkv, page, W, Pll, workgroups);
-  const int P = static_cast<int>(Pll);
-  const std::vector<int> lens = detail::attn_paged_lens(B, L, ragged);
+  using C = AttnCacheBf16;
+  const detail::AttnPagedTimed t("run_attn_paged", attn_paged_shape, B, Hq, Hkv, L, page,
+                                 iters, ragged, workgroups);
   const float scale = detail::attn_default_scale();
-  std::vector<float> q(static_cast<size_t>(B) * Hq * kAttnD);
-  detail::attn_pattern_q(q.data(), B, Hq);
-  double keys = 0;
-  for (int len : lens) keys += len;
-
-  AttnPagedResult r;
-  const size_t groups = static_cast<size_t>(B) * Hkv * W * page * kAttnD / 8;
-  // the rates of `iters` launches in ms, and the 16 rows of the output at dout
-  auto report = [&](float ms, const float* dout) {
-    const double sec = ms * 1e-3;
-    r.steps_per_s = iters / sec;
-    r.tok_per_s = r.steps_per_s * B;
-    r.kv_gb_s = keys * Hkv * kAttnD * 2.0 * 2.0 * iters / sec / 1e9;
-    std::vector<float> got(kAttnD), want(kAttnD);
-    const size_t rows = static_cast<size_t>(B) * Hq;
-    for (int t = 0; t < 16; ++t) {
-      const size_t row = detail::attn_spread_row(t, rows);
-      HIP_CHECK(hipMemcpy(got.data(), dout + row * kAttnD, kAttnD * sizeof(float),
-                          hipMemcpyDeviceToHost));
-      const int b = static_cast<int>(row / Hq);
-      detail::attn_pattern_row(want.data(), b, static_cast<int>(row % Hq), Hq / Hkv,
-                               lens[b]);
-      for (int d = 0; d < kAttnD; ++d)
-        detail::note_err(r.max_err, std::fabs(static_cast<double>(got[d]) -
-                                              static_cast<double>(want[d])));
-    }
+  const size_t groups = static_cast<size_t>(B) * Hkv * t.W * page * kAttnD / C::kLane;
+  auto fill = [&](auto& p, const int* table, int shift) {
+    hipLaunchKernelGGL(attn_paged_fill_kernel, dim3(grid_for(groups)), dim3(kBlock), 0, 0,
+                       p.dk.template as<uint16_t>(), p.dvt.template as<uint16_t>(), table,
+                       p.dlens.template as<const int>(), Hkv, t.W, shift, groups);
   };
+  AttnPagedResult r;
   if (contiguous) {
     if (L % page != 0)
       throw std::invalid_argument("run_attn_paged: contiguous needs L % page == 0");
     detail::AttnProblem c(B, Hq, Hkv, L, 0, device);
     c.alloc();
-    c.upload_q_lens(q.data(), lens.data());
-    hipLaunchKernelGGL(attn_paged_fill_kernel, dim3(grid_for(groups)), dim3(kBlock), 0, 0,
-                       c.dk.as<uint16_t>(), c.dvt.as<uint16_t>(),
-                       static_cast<const int*>(nullptr), c.dlens.as<const int>(), Hkv, W,
-                       __builtin_ctz(page / kAttnChunk), groups);
+    c.upload_q_lens(t.q.data(), t.lens.data());
+    fill(c, nullptr, __builtin_ctz(page / kAttnChunk));
     HIP_CHECK(hipGetLastError());
-    report(detail::time_launches(iters, [&c, scale] { c.launch(scale); }),
-           c.dout.as<float>());
+    t.report(r, detail::time_launches(iters, [&c, scale] { c.launch(scale); }),
+             c.dout.as<float>(), 2 * sizeof(C::Elem));
     r.items = B * c.splits;
     return r;
   }
-  detail::AttnPagedProblem p(B, Hq, Hkv, page, W, P, workgroups, device);
-  const std::vector<int> table = detail::attn_paged_scrambled_table(B, W, P);
-  p.alloc();
-  p.upload_q_table(q.data(), table.data(), lens.data());
-  hipLaunchKernelGGL(attn_paged_fill_kernel, dim3(grid_for(groups)), dim3(kBlock), 0, 0,
-                     p.dk.as<uint16_t>(), p.dvt.as<uint16_t>(), p.dtable.as<const int>(),
-                     p.dlens.as<const int>(), Hkv, W, p.shift, groups);
-  HIP_CHECK(hipGetLastError());
-  report(detail::time_launches(iters, [&p, scale] { p.launch(scale); }),
-         p.dout.as<float>());
-  r.items = p.items();
+  detail::AttnPagedBf16Problem p(B, Hq, Hkv, page, t.W, t.P, workgroups, device);
+  const float ms = t.time(
+      r, p, [&] { fill(p, p.dtable.as<const int>(), p.shift()); },
+      [&p, scale] { p.launch(scale); });
+  t.report(r, ms, p.dout.as<float>(), 2 * sizeof(C::Elem));
   return r;
 }
 

@@ -310,6 +310,53 @@ static void print_attn_check(const char* cmd, const AttnArgs& a, const AttnCheck
               json_num(c.max_rel));
 }
 
+// paged / paged8 [B HQ HKV L [PAGE [ITERS [WORKGROUPS]]]]: the verbs differ in
+// the functions they call and in the fields that the fp8 one adds
+static bool print_timed_paged(bool fp8, int argc, char** argv) {
+  AttnArgs a{32, 64, 8, 4096};
+  a.parse(argc, argv);
+  int page = argc > 6 ? std::atoi(argv[6]) : 64;
+  int iters = argc > 7 ? std::atoi(argv[7]) : 10;
+  int workgroups = argc > 8 ? std::atoi(argv[8]) : 0;
+  AttnCheck c = fp8 ? run_attn_paged_fp8_check(4, 8, 2, 300, 64)
+                    : run_attn_paged_check(4, 8, 2, 300, 64);
+  AttnPagedResult r;
+  double us = 0, bf16_us = 0, quant_rel = 0;  // what the fp8 run adds
+  if (fp8) {
+    AttnPaged8Result r8 =
+        run_attn_paged_fp8(a.b, a.hq, a.hkv, a.len, page, iters, false, workgroups);
+    r = r8;
+    us = r8.us, bf16_us = r8.bf16_us, quant_rel = r8.quant_rel;
+  } else {
+    r = run_attn_paged(a.b, a.hq, a.hkv, a.len, page, iters, false, workgroups);
+  }
+  double max_err = r.max_err > c.max_err ? r.max_err : c.max_err;
+  bool ok = max_err == 0.0 && c.max_rel <= kAttnRelBound;
+  a.print_head(fp8 ? "paged8" : "paged", ok);
+  std::printf("\"page\": %d, \"iters\": %d, \"items\": %d, ", page, iters, r.items);
+  if (fp8) std::printf("\"us\": %.2f, \"bf16_us\": %.2f, ", us, bf16_us);
+  std::printf("\"kv_gb_per_s\": %.1f, \"steps_per_s\": %.1f, \"tok_per_s\": %.1f, ",
+              r.kv_gb_s, r.steps_per_s, r.tok_per_s);
+  if (fp8) std::printf("\"quant_rel\": %g, ", json_num(quant_rel));
+  std::printf("\"max_err\": %g, \"max_rel\": %g}\n", json_num(max_err),
+              json_num(c.max_rel));
+  return ok;
+}
+
+// serve's paged / paged8 [B HQ HKV L [PAGE]]
+static void print_paged_check(bool fp8, std::istringstream& iss) {
+  AttnArgs a{4, 8, 2, 300};
+  a.parse(iss);
+  int page = 64, tp;
+  if (iss >> tp) page = tp;
+  char extra[32];
+  std::snprintf(extra, sizeof(extra), "\"page\": %d, ", page);
+  print_attn_check(fp8 ? "paged8" : "paged", a,
+                   fp8 ? run_attn_paged_fp8_check(a.b, a.hq, a.hkv, a.len, page)
+                       : run_attn_paged_check(a.b, a.hq, a.hkv, a.len, page),
+                   extra);
+}
+
 // one census run: the XCDs that ran a workgroup, and the per-XCD counts as the
 // elements of a JSON array
 struct Census {
@@ -386,45 +433,8 @@ int main(int argc, char** argv) {
           iters, r.kv_gb_s, r.steps_per_s, r.tok_per_s, json_num(max_err),
           json_num(c.max_rel));
       return ok ? 0 : 1;
-    } else if (std::strcmp(cmd, "paged") == 0) {
-      AttnArgs a{32, 64, 8, 4096};
-      a.parse(argc, argv);
-      int page = argc > 6 ? std::atoi(argv[6]) : 64;
-      int iters = argc > 7 ? std::atoi(argv[7]) : 10;
-      int workgroups = argc > 8 ? std::atoi(argv[8]) : 0;
-      AttnCheck c = run_attn_paged_check(4, 8, 2, 300, 64);
-      AttnPagedResult r =
-          run_attn_paged(a.b, a.hq, a.hkv, a.len, page, iters, false, workgroups);
-      double max_err = r.max_err > c.max_err ? r.max_err : c.max_err;
-      bool ok = max_err == 0.0 && c.max_rel <= kAttnRelBound;
-      a.print_head("paged", ok);
-      std::printf(
-          "\"page\": %d, \"iters\": %d, \"items\": %d, \"kv_gb_per_s\": %.1f, "
-          "\"steps_per_s\": %.1f, \"tok_per_s\": %.1f, \"max_err\": %g, "
-          "\"max_rel\": %g}\n",
-          page, iters, r.items, r.kv_gb_s, r.steps_per_s, r.tok_per_s, json_num(max_err),
-          json_num(c.max_rel));
-      return ok ? 0 : 1;
-    } else if (std::strcmp(cmd, "paged8") == 0) {
-      AttnArgs a{32, 64, 8, 4096};
-      a.parse(argc, argv);
-      int page = argc > 6 ? std::atoi(argv[6]) : 64;
-      int iters = argc > 7 ? std::atoi(argv[7]) : 10;
-      int workgroups = argc > 8 ? std::atoi(argv[8]) : 0;
-      AttnCheck c = run_attn_paged_fp8_check(4, 8, 2, 300, 64);
-      AttnPaged8Result r =
-          run_attn_paged_fp8(a.b, a.hq, a.hkv, a.len, page, iters, false, workgroups);
-      double max_err = r.max_err > c.max_err ? r.max_err : c.max_err;
-      bool ok = max_err == 0.0 && c.max_rel <= kAttnRelBound;
-      a.print_head("paged8", ok);
-      std::printf(
-          "\"page\": %d, \"iters\": %d, \"items\": %d, \"us\": %.2f, "
-          "\"bf16_us\": %.2f, \"kv_gb_per_s\": %.1f, \"steps_per_s\": %.1f, "
-          "\"tok_per_s\": %.1f, \"quant_rel\": %g, \"max_err\": %g, "
-          "\"max_rel\": %g}\n",
-          page, iters, r.items, r.us, r.bf16_us, r.kv_gb_s, r.steps_per_s, r.tok_per_s,
-          json_num(r.quant_rel), json_num(max_err), json_num(c.max_rel));
-      return ok ? 0 : 1;
+    } else if (std::strcmp(cmd, "paged") == 0 || std::strcmp(cmd, "paged8") == 0) {
+      return print_timed_paged(std::strcmp(cmd, "paged8") == 0, argc, argv) ? 0 : 1;
     } else if (std::strcmp(cmd, "prefill") == 0) {
       AttnArgs a{8, 64, 8, 4096};
       a.parse(argc, argv);
@@ -514,25 +524,8 @@ int main(int argc, char** argv) {
             AttnArgs a{2, 8, 2, 300};
             a.parse(iss);
             print_attn_check("attn", a, run_attn_check(a.b, a.hq, a.hkv, a.len), "");
-          } else if (verb == "paged") {
-            AttnArgs a{4, 8, 2, 300};
-            a.parse(iss);
-            int page = 64, tp;
-            if (iss >> tp) page = tp;
-            char extra[32];
-            std::snprintf(extra, sizeof(extra), "\"page\": %d, ", page);
-            print_attn_check("paged", a,
-                             run_attn_paged_check(a.b, a.hq, a.hkv, a.len, page), extra);
-          } else if (verb == "paged8") {
-            AttnArgs a{4, 8, 2, 300};
-            a.parse(iss);
-            int page = 64, tp;
-            if (iss >> tp) page = tp;
-            char extra[32];
-            std::snprintf(extra, sizeof(extra), "\"page\": %d, ", page);
-            print_attn_check("paged8", a,
-                             run_attn_paged_fp8_check(a.b, a.hq, a.hkv, a.len, page),
-                             extra);
+          } else if (verb == "paged" || verb == "paged8") {
+            print_paged_check(verb == "paged8", iss);
           } else if (verb == "prefill") {
             AttnArgs a{1, 4, 2, 200};
             a.parse(iss);

@@ -326,6 +326,56 @@ py::dict attn_timed_dict(int batch, int hq, int hkv, int length, int iters) {
   return d;
 }
 
+// the report of one of the timed paged runs; r8: what the fp8 one adds
+py::dict paged_timed_dict(int batch, int hq, int hkv, int length, int iters, int page,
+                          bool ragged, const payload::AttnPagedResult& r,
+                          const payload::AttnPaged8Result* r8 = nullptr) {
+  py::dict d = attn_timed_dict(batch, hq, hkv, length, iters);
+  d["page"] = page;
+  d["ragged"] = ragged;
+  d["items"] = r.items;
+  if (r8) {
+    d["us"] = r8->us;
+    d["bf16_us"] = r8->bf16_us;
+  }
+  d["kv_gb_per_s"] = r.kv_gb_s;
+  d["steps_per_s"] = r.steps_per_s;
+  d["tok_per_s"] = r.tok_per_s;
+  if (r8) d["quant_rel"] = r8->quant_rel;
+  d["max_err"] = r.max_err;
+  return d;
+}
+
+// The operands of the two paged entries: q (B,Hq,128), the two pools
+// (P,Hkv,page,128) and alike (`pools` names them in the messages), table (B,W)
+// and lens (B,) integer, narrowed. TypeError or ValueError, in the order the
+// entries always raised them; the shape limits are the caller's and come after.
+// Narrowing here, ahead of them, raises nothing (paged_narrow cannot): it only
+// copies a table once that the limits may then reject.
+struct PagedOperands {
+  py::ssize_t B, Hq, Hkv, page, W, P;
+  std::vector<int> tab, lens;
+};
+template <class Pool>
+PagedOperands paged_operands(const char* who, const char* pools, const f32_array& q,
+                             const Pool& k, const Pool& v, const py::object& table_,
+                             const py::object& lens_) {
+  const std::string w(who), kv(pools);
+  auto table = paged_ints(who, "table", table_, 2);
+  auto lens_arr = paged_ints(who, "lens", lens_, 1);
+  if (q.ndim() != 3) throw py::value_error(w + ": q must be (B,Hq,128)");
+  if (k.ndim() != 4 || v.ndim() != 4)
+    throw py::value_error(w + ": " + kv + " must be (P,Hkv,page,128)");
+  if (q.shape(2) != payload::kAttnD || k.shape(3) != payload::kAttnD)
+    throw py::value_error(w + ": head dim must be 128");
+  for (int i = 0; i < 4; ++i)
+    if (k.shape(i) != v.shape(i)) throw py::value_error(w + ": " + kv + " differ in shape");
+  if (table.shape(0) != q.shape(0) || lens_arr.shape(0) != q.shape(0))
+    throw py::value_error(w + ": table must be (B,W) and lens (B,)");
+  return {q.shape(0), q.shape(1), k.shape(1), k.shape(2), table.shape(1), k.shape(0),
+          paged_narrow(table), paged_narrow(lens_arr)};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_payload, m) {
@@ -1089,24 +1139,10 @@ PYBIND11_MODULE(_payload, m) {
       [](f32_array q, f32_array k_pages, f32_array v_pages, py::object table_,
          py::object lens_, py::object scale, int workgroups, int device) {
         const char* who = "attn_paged_decode";
-        const std::string w(who);
-        auto table = paged_ints(who, "table", table_, 2);
-        auto lens_arr = paged_ints(who, "lens", lens_, 1);
-        if (q.ndim() != 3) throw py::value_error(w + ": q must be (B,Hq,128)");
-        if (k_pages.ndim() != 4 || v_pages.ndim() != 4)
-          throw py::value_error(w + ": k_pages and v_pages must be (P,Hkv,page,128)");
-        if (q.shape(2) != payload::kAttnD || k_pages.shape(3) != payload::kAttnD)
-          throw py::value_error(w + ": head dim must be 128");
-        for (int i = 0; i < 4; ++i)
-          if (k_pages.shape(i) != v_pages.shape(i))
-            throw py::value_error(w + ": k_pages and v_pages differ in shape");
-        const py::ssize_t B = q.shape(0), Hq = q.shape(1), P = k_pages.shape(0),
-                          Hkv = k_pages.shape(1), page = k_pages.shape(2),
-                          W = table.shape(1);
-        if (table.shape(0) != B || lens_arr.shape(0) != B)
-          throw py::value_error(w + ": table must be (B,W) and lens (B,)");
+        const PagedOperands a =
+            paged_operands(who, "k_pages and v_pages", q, k_pages, v_pages, table_, lens_);
+        const py::ssize_t B = a.B, Hq = a.Hq, Hkv = a.Hkv, page = a.page, W = a.W, P = a.P;
         payload::attn_paged_shape(B, Hq, Hkv, page, W, P, workgroups);
-        const std::vector<int> tab = paged_narrow(table), lens = paged_narrow(lens_arr);
         const float sc = attn_scale(who, scale);
         const float* pq = q.data();
         const float* pk = k_pages.data();
@@ -1115,7 +1151,7 @@ PYBIND11_MODULE(_payload, m) {
         float* po = o.mutable_data();
         {
           py::gil_scoped_release rel;
-          payload::attn_paged_decode(pq, pk, pv, tab.data(), lens.data(), po,
+          payload::attn_paged_decode(pq, pk, pv, a.tab.data(), a.lens.data(), po,
                                      static_cast<int>(B), static_cast<int>(Hq),
                                      static_cast<int>(Hkv), static_cast<int>(page),
                                      static_cast<int>(W), static_cast<int>(P), sc,
@@ -1195,15 +1231,7 @@ PYBIND11_MODULE(_payload, m) {
           r = payload::run_attn_paged(batch, hq, hkv, length, page, iters, ragged,
                                       workgroups, device, contiguous);
         }
-        py::dict d = attn_timed_dict(batch, hq, hkv, length, iters);
-        d["page"] = page;
-        d["ragged"] = ragged;
-        d["items"] = r.items;
-        d["kv_gb_per_s"] = r.kv_gb_s;
-        d["steps_per_s"] = r.steps_per_s;
-        d["tok_per_s"] = r.tok_per_s;
-        d["max_err"] = r.max_err;
-        return d;
+        return paged_timed_dict(batch, hq, hkv, length, iters, page, ragged, r);
       },
       py::arg("batch") = 32, py::arg("hq") = 64, py::arg("hkv") = 8,
       py::arg("length") = 4096, py::arg("page") = 64, py::arg("iters") = 10,
@@ -1225,28 +1253,14 @@ PYBIND11_MODULE(_payload, m) {
          f32_array v_scale, py::object table_, py::object lens_, py::object scale,
          int workgroups, int device) {
         const char* who = "attn_paged_decode_fp8";
-        const std::string w(who);
         auto k_codes = uint8_operand(who, "k_codes", k_codes_);
         auto v_codes = uint8_operand(who, "v_codes", v_codes_);
-        auto table = paged_ints(who, "table", table_, 2);
-        auto lens_arr = paged_ints(who, "lens", lens_, 1);
-        if (q.ndim() != 3) throw py::value_error(w + ": q must be (B,Hq,128)");
-        if (k_codes.ndim() != 4 || v_codes.ndim() != 4)
-          throw py::value_error(w + ": k_codes and v_codes must be (P,Hkv,page,128)");
-        if (q.shape(2) != payload::kAttnD || k_codes.shape(3) != payload::kAttnD)
-          throw py::value_error(w + ": head dim must be 128");
-        for (int i = 0; i < 4; ++i)
-          if (k_codes.shape(i) != v_codes.shape(i))
-            throw py::value_error(w + ": k_codes and v_codes differ in shape");
-        const py::ssize_t B = q.shape(0), Hq = q.shape(1), P = k_codes.shape(0),
-                          Hkv = k_codes.shape(1), page = k_codes.shape(2),
-                          W = table.shape(1);
-        if (table.shape(0) != B || lens_arr.shape(0) != B)
-          throw py::value_error(w + ": table must be (B,W) and lens (B,)");
+        const PagedOperands a =
+            paged_operands(who, "k_codes and v_codes", q, k_codes, v_codes, table_, lens_);
+        const py::ssize_t B = a.B, Hq = a.Hq, Hkv = a.Hkv, page = a.page, W = a.W, P = a.P;
         scale_vector(who, "k_scale", k_scale, static_cast<int>(Hkv));
         scale_vector(who, "v_scale", v_scale, static_cast<int>(Hkv));
         payload::attn_paged_fp8_shape(B, Hq, Hkv, page, W, P, workgroups);
-        const std::vector<int> tab = paged_narrow(table), lens = paged_narrow(lens_arr);
         const float sc = attn_scale(who, scale);
         const float* pq = q.data();
         const uint8_t* pk = k_codes.data();
@@ -1257,8 +1271,8 @@ PYBIND11_MODULE(_payload, m) {
         float* po = o.mutable_data();
         {
           py::gil_scoped_release rel;
-          payload::attn_paged_decode_fp8(pq, pk, pv, pks, pvs, tab.data(), lens.data(), po,
-                                         static_cast<int>(B), static_cast<int>(Hq),
+          payload::attn_paged_decode_fp8(pq, pk, pv, pks, pvs, a.tab.data(), a.lens.data(),
+                                         po, static_cast<int>(B), static_cast<int>(Hq),
                                          static_cast<int>(Hkv), static_cast<int>(page),
                                          static_cast<int>(W), static_cast<int>(P), sc,
                                          workgroups, device);
@@ -1318,18 +1332,7 @@ PYBIND11_MODULE(_payload, m) {
           r = payload::run_attn_paged_fp8(batch, hq, hkv, length, page, iters, ragged,
                                           workgroups, device);
         }
-        py::dict d = attn_timed_dict(batch, hq, hkv, length, iters);
-        d["page"] = page;
-        d["ragged"] = ragged;
-        d["items"] = r.items;
-        d["us"] = r.us;
-        d["bf16_us"] = r.bf16_us;
-        d["kv_gb_per_s"] = r.kv_gb_s;
-        d["steps_per_s"] = r.steps_per_s;
-        d["tok_per_s"] = r.tok_per_s;
-        d["quant_rel"] = r.quant_rel;
-        d["max_err"] = r.max_err;
-        return d;
+        return paged_timed_dict(batch, hq, hkv, length, iters, page, ragged, r, &r);
       },
       py::arg("batch") = 32, py::arg("hq") = 64, py::arg("hkv") = 8,
       py::arg("length") = 4096, py::arg("page") = 64, py::arg("iters") = 10,

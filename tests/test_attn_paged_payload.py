@@ -266,6 +266,75 @@ def test_prefix_sharing(payload, dense):
     assert np.isfinite(out).all() and (err <= REL).all()
 
 
+@pytest.mark.gpu
+def test_bf16_and_fp8_caches_agree_on_the_same_values(payload):
+    """The two paged kernels run the same chunk step, each in its own body, so
+    on the same real numbers (e4m3 codes under scales of 1, and the decoded
+    codes as bf16 pages) they may differ only through how the keys are grouped.
+    With lengths that are multiples of 64 and one work item per sequence both
+    plans cut the same key ranges, but a wave takes 32-key chunks round-robin
+    in one kernel and 64-key chunks in the other, so the partials differ and
+    bit-equality of the merged result cannot be had: on random data a weight is
+    rounded to bf16 under one running maximum here and another there, and the
+    two results are 2e-4 max |v| apart (measured, on the unfolded kernels too).
+
+    So the data takes the weights' rounding out. K holds the codes of the
+    integers -4 .. 4, every q row is +-1 at two places, and scale is float32
+    ln 2, for which scale * log2(e) is exactly 1 in fp32: every score, every
+    running maximum and every difference of the two is an integer, every weight
+    an exact power of two that bf16 holds, alpha and the merge weights too. V
+    draws from all non-negative non-NaN codes, so no sum cancels. What is left
+    are the fp32 roundings of non-negative sums taken in another order: per
+    result at most two chunk accumulations per wave, four merge terms and one
+    division, for o and for l. Counting the MFMA's inner sum as up to four
+    roundings that is below 16 half-ulps twice over, so the two results are
+    asserted within 16 ulps of each other, element by element, and each within
+    2^-8 max |v| of fp64. A wrong key index, l update, guard or rescale in
+    either body moves a result by whole weights, not ulps."""
+    lens, hq, hkv, page = [64, 128, 192], 4, 2, 64
+    for chunk in (32, 64):
+        items, _ = payload.attn_paged_plan(lens, 1, chunk)
+        keys = [(b, c0 * chunk, c1 * chunk) for b, c0, c1 in items.tolist()]
+        assert keys == [(b, 0, n) for b, n in enumerate(lens)]
+    rng = np.random.default_rng(8)
+    small = payload.to_e4m3(np.arange(-4, 5, dtype=np.float32))
+    W = max(lens) // page
+    P = len(lens) * W
+    table = rng.permutation(P).reshape(len(lens), W).astype(np.int32)
+    kc = rng.choice(small, (P, hkv, page, D))
+    vc = rng.integers(0, 0x7F, (P, hkv, page, D), dtype=np.uint8)
+    k, v = payload.from_e4m3(kc), payload.from_e4m3(vc)
+    assert np.array_equal(k, np.rint(k)) and np.abs(k).max() == 4 and v.min() == 0
+    q = np.zeros((len(lens), hq, D), np.float32)
+    for row in q.reshape(-1, D):
+        row[rng.choice(D, 2, replace=False)] = rng.choice([-1.0, 1.0], 2)
+    one = np.ones(hkv, np.float32)
+    ln2 = float(np.float32(np.log(2.0)))
+    assert np.float32(ln2) * np.float32(1.4426950408889634) == np.float32(1.0)
+    a = payload.attn_paged_decode(q, k, v, table, lens, scale=ln2, workgroups=1)
+    b = payload.attn_paged_decode_fp8(q, kc, vc, one, one, table, lens, scale=ln2,
+                                      workgroups=1)
+    ref = np.empty(a.shape)
+    n_eff = []
+    for i, n in enumerate(lens):
+        kd, vd = (x[table[i]].transpose(1, 0, 2, 3).reshape(hkv, W * page, D)[:, :n]
+                  .astype(np.float64) for x in (k, v))
+        for h in range(hq):
+            sc = kd[h // (hq // hkv)] @ q[i, h].astype(np.float64)
+            w = np.exp2(sc - sc.max())
+            ref[i, h] = (w @ vd[h // (hq // hkv)]) / w.sum()
+            n_eff.append(w.sum() ** 2 / (w * w).sum())
+    vmax = np.abs(v).max()
+    err_a, err_b = (np.abs(x.astype(np.float64) - ref).max() / vmax for x in (a, b))
+    ulps = np.abs(a - b) / np.spacing(np.maximum(np.abs(a), np.abs(b)))
+    print(f"\nbf16 {err_a:.3e} fp8 {err_b:.3e} apart {ulps.max():.1f} ulps, keys with "
+          f"weight {min(n_eff):.1f} .. {max(n_eff):.1f}, "
+          f"bit-identical {np.array_equal(a.view(np.uint32), b.view(np.uint32))}")
+    assert np.isfinite(a).all() and np.isfinite(b).all()
+    assert err_a <= REL and err_b <= REL
+    assert ulps.max() <= 16
+
+
 # ---- GPU: the self-check, the timed run, the binary, serve, the runner -------
 
 @pytest.mark.gpu
