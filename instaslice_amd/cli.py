@@ -20,7 +20,7 @@
     python -m instaslice_amd cordon     --store HOST:PORT --node N [--uncordon]
     python -m instaslice_amd payload    [info|vecadd|membw|busy|census|gemm|
                                          dgemm|igemm|mxgemm|mx4gemm|moe|attn|
-                                         paged|paged8|prefill|memcheck|
+                                         paged|paged8|prefill|extend|memcheck|
                                          verify] ...
     python -m instaslice_amd verify     --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
@@ -44,6 +44,8 @@
     python -m instaslice_amd paged8     --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
     python -m instaslice_amd prefill   --profile NAME
+                                        [--visible-devices UUID_OR_INDEX]
+    python -m instaslice_amd extend     --profile NAME
                                         [--visible-devices UUID_OR_INDEX]
 
 NODE_NAME env is honored for the daemonset (downward-API parity with
@@ -480,6 +482,13 @@ def cmd_prefill(args) -> int:
     return _probe(args, "run_prefill")
 
 
+def cmd_extend(args) -> int:
+    """Run the paged chunked-prefill (extend) attention payload inside the
+    visible partition and judge it against the requested profile; prints the
+    judged JSON, exit 0 iff ok."""
+    return _probe(args, "run_extend")
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="instaslice-amd")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -691,6 +700,17 @@ def main(argv=None) -> int:
                    help="ROCR_VISIBLE_DEVICES for the probe (partition UUID "
                         "or index); default: inherit the environment")
     p.set_defaults(fn=cmd_prefill)
+
+    p = sub.add_parser("extend",
+                       help="check and time paged chunked-prefill attention (a "
+                            "run of new tokens per sequence over the paged KV "
+                            "cache) in the visible partition, judge it against "
+                            "a profile")
+    p.add_argument("--profile", required=True, help="e.g. cpx-1x36")
+    p.add_argument("--visible-devices", default=None,
+                   help="ROCR_VISIBLE_DEVICES for the probe (partition UUID "
+                        "or index); default: inherit the environment")
+    p.set_defaults(fn=cmd_extend)
 
     args = ap.parse_args(argv)
     return args.fn(args)

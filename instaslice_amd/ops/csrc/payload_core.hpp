@@ -82,6 +82,14 @@
 //                between, exact-checked, bound-checked and timed: the
 //                compute-bound half of serving (payload_prefill.hpp, included
 //                below)
+//   extend      paged chunked-prefill attention: a ragged run of new tokens per
+//                sequence over the paged cache plus, causally, each other. The
+//                pool's chunk images reached through the block table, staged
+//                through double-buffered LDS as they stand and shared by 128
+//                (token, head) columns on the 16x16x32 bf16 MFMA, the item
+//                list planned on the device; exact-checked, bound-checked and
+//                timed: the step between decode and a cold prompt
+//                (payload_attn_extend.hpp, included below)
 //
 // Kernel style per the CDNA4 playbook: 256-thread blocks (4 waves of 64),
 // float4 (dwordx4) streaming accesses for coalescing, grid-strided loops
@@ -650,3 +658,7 @@ inline int device_count() {
 // prefill attention payload: the decode one's head dim, patterns, scale and
 // shared host pieces
 #include "payload_prefill.hpp"
+
+// paged chunked-prefill attention payload: the paged one's problem struct,
+// check case and argument checks, prefill's patterns and bf16 pack
+#include "payload_attn_extend.hpp"

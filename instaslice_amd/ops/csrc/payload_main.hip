@@ -128,6 +128,25 @@
 //                                             flattering rate, for comparison
 //                                             only); exit 1 unless max_err ==
 //                                             0 and max_rel <= 2^-8
+//   instaslice-payload extend [B HQ HKV L [N [PAGE [ITERS [RAGGED]]]]]
+//                                             paged chunked-prefill attention:
+//                                             the last N of a sequence's L
+//                                             keys are new tokens that attend
+//                                             to the paged cache and, causally,
+//                                             to each other: the self-check at
+//                                             8 8 2 300, page 64, on ragged
+//                                             lengths and runs, then a timed
+//                                             run on the dense pattern (default
+//                                             8 64 8 4096, N 1024, page 64, 10
+//                                             iters; plan and extend per
+//                                             launch) with 16 rows checked
+//                                             against fp64; "new" is N, "items"
+//                                             the plan's item count, TFLOP/s
+//                                             counts the unmasked pairs only;
+//                                             RAGGED 1 gives every eighth
+//                                             sequence L keys and the rest L /
+//                                             8; exit 1 unless max_err == 0 and
+//                                             max_rel <= 2^-8
 //   instaslice-payload verify [XCDS]          census + vecadd + gemm check +
 //                                             membw + timed gemm in one JSON
 //                                             line; XCDS (0 or absent: not
@@ -357,6 +376,28 @@ static void print_paged_check(bool fp8, std::istringstream& iss) {
                    extra);
 }
 
+// extend [B HQ HKV L [N [PAGE [ITERS [RAGGED]]]]]: the timed run
+static bool print_timed_extend(int argc, char** argv) {
+  AttnArgs a{8, 64, 8, 4096};
+  a.parse(argc, argv);
+  int n = argc > 6 ? std::atoi(argv[6]) : 1024;
+  int page = argc > 7 ? std::atoi(argv[7]) : 64;
+  int iters = argc > 8 ? std::atoi(argv[8]) : 10;
+  bool ragged = argc > 9 && std::atoi(argv[9]) != 0;
+  AttnCheck c = run_attn_extend_check(8, 8, 2, 300, 64);
+  AttnExtendResult r = run_attn_extend(a.b, a.hq, a.hkv, a.len, n, page, iters, ragged);
+  double max_rel = r.max_rel > c.max_rel ? r.max_rel : c.max_rel;
+  if (std::isnan(r.max_rel) || std::isnan(c.max_rel)) max_rel = INFINITY;
+  bool ok = c.max_err == 0.0 && max_rel <= kAttnRelBound;
+  a.print_head("extend", ok);
+  std::printf(
+      "\"new\": %d, \"page\": %d, \"iters\": %d, \"ragged\": %s, \"items\": %d, "
+      "\"tflops\": %.2f, \"tok_per_s\": %.1f, \"max_err\": %g, \"max_rel\": %g}\n",
+      n, page, iters, ragged ? "true" : "false", r.items, r.tflops, r.tok_per_s,
+      json_num(c.max_err), json_num(max_rel));
+  return ok;
+}
+
 // one census run: the XCDs that ran a workgroup, and the per-XCD counts as the
 // elements of a JSON array
 struct Census {
@@ -453,6 +494,8 @@ int main(int argc, char** argv) {
           iters, causal ? "true" : "false", r.tflops, r.tok_per_s, json_num(c.max_err),
           json_num(max_rel));
       return ok ? 0 : 1;
+    } else if (std::strcmp(cmd, "extend") == 0) {
+      return print_timed_extend(argc, argv) ? 0 : 1;
     } else if (std::strcmp(cmd, "memcheck") == 0) {
       size_t bytes = argc > 2 ? std::strtoull(argv[2], nullptr, 10) : (size_t{1} << 30);
       int passes = argc > 3 ? std::atoi(argv[3]) : 1;
@@ -500,8 +543,8 @@ int main(int argc, char** argv) {
       //   vecadd <n> | busy <ms> | gemm [M N K] | dgemm [M N K] |
       //   igemm [M N K] | mxgemm [M N K] | mx4gemm [M N K] |
       //   moe [T N K E TOPK] | attn [B HQ HKV L] | paged [B HQ HKV L [PAGE]] |
-      //   paged8 [B HQ HKV L [PAGE]] | prefill [B HQ HKV L] | memcheck [BYTES] |
-      //   ping | quit
+      //   paged8 [B HQ HKV L [PAGE]] | prefill [B HQ HKV L] | extend |
+      //   memcheck [BYTES] | ping | quit
       std::string line;
       while (std::getline(std::cin, line)) {
         std::istringstream iss(line);
@@ -531,6 +574,10 @@ int main(int argc, char** argv) {
             a.parse(iss);
             print_attn_check("prefill", a, run_prefill_check(a.b, a.hq, a.hkv, a.len),
                              "\"causal\": true, ");
+          } else if (verb == "extend") {
+            AttnArgs a{8, 8, 2, 300};
+            print_attn_check("extend", a, run_attn_extend_check(a.b, a.hq, a.hkv, a.len, 64),
+                             "\"page\": 64, ");
           } else if (verb == "memcheck") {
             size_t bytes = size_t{64} << 20;
             iss >> bytes;

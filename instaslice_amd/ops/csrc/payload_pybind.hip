@@ -381,7 +381,7 @@ PagedOperands paged_operands(const char* who, const char* pools, const f32_array
 PYBIND11_MODULE(_payload, m) {
   m.doc() = "gfx950 HIP payload kernels (vecadd / membw / busy / xcd census / gemm / "
             "dgemm / igemm / mxgemm / mx4gemm / moe / memcheck / attn / paged / paged8 / "
-            "prefill)";
+            "prefill / extend)";
 
   m.def("device_count", &payload::device_count,
         "Number of visible HIP devices (0 if no GPU/driver)");
@@ -1441,4 +1441,136 @@ PYBIND11_MODULE(_payload, m) {
       "timed prefill attention on the dense hash pattern (device-filled; pattern=1 "
       "times the low-entropy selection pattern instead), TFLOP/s over the unmasked "
       "pairs only, 16 spread output rows checked against fp64");
+
+  // ---- paged chunked-prefill (extend) attention --------------------------------
+
+  m.def(
+      "attn_paged_extend",
+      [](f32_array q, f32_array k_pages, f32_array v_pages, py::object table_,
+         py::object lens_, py::object qlens_, py::object scale, int device) {
+        const char* who = "attn_paged_extend";
+        const std::string w(who);
+        auto table = paged_ints(who, "table", table_, 2);
+        auto lens_arr = paged_ints(who, "lens", lens_, 1);
+        auto qlens_arr = paged_ints(who, "qlens", qlens_, 1);
+        if (q.ndim() != 3) throw py::value_error(w + ": q must be (Tq,Hq,128)");
+        if (k_pages.ndim() != 4 || v_pages.ndim() != 4)
+          throw py::value_error(w + ": k_pages and v_pages must be (P,Hkv,page,128)");
+        if (q.shape(2) != payload::kAttnD || k_pages.shape(3) != payload::kAttnD)
+          throw py::value_error(w + ": head dim must be 128");
+        for (int i = 0; i < 4; ++i)
+          if (k_pages.shape(i) != v_pages.shape(i))
+            throw py::value_error(w + ": k_pages and v_pages differ in shape");
+        const py::ssize_t B = table.shape(0), W = table.shape(1), Tq = q.shape(0),
+                          Hq = q.shape(1), P = k_pages.shape(0), Hkv = k_pages.shape(1),
+                          page = k_pages.shape(2);
+        if (lens_arr.shape(0) != B || qlens_arr.shape(0) != B)
+          throw py::value_error(w + ": table must be (B,W), lens and qlens (B,)");
+        payload::attn_extend_shape(B, Hq, Hkv, page, W, P, Tq);
+        const float sc = attn_scale(who, scale);
+        const std::vector<int> tab = paged_narrow(table), lens = paged_narrow(lens_arr),
+                               qlens = paged_narrow(qlens_arr);
+        const float* pq = q.data();
+        const float* pk = k_pages.data();
+        const float* pv = v_pages.data();
+        py::array_t<float> o({Tq, Hq, static_cast<py::ssize_t>(payload::kAttnD)});
+        float* po = o.mutable_data();
+        {
+          py::gil_scoped_release rel;
+          payload::attn_paged_extend(pq, pk, pv, tab.data(), lens.data(), qlens.data(), po,
+                                     static_cast<int>(B), static_cast<int>(Hq),
+                                     static_cast<int>(Hkv), static_cast<int>(page),
+                                     static_cast<int>(W), static_cast<int>(P),
+                                     static_cast<int>(Tq), sc, device);
+        }
+        return o;
+      },
+      py::arg("q"), py::arg("k_pages"), py::arg("v_pages"), py::arg("table"),
+      py::arg("lens"), py::arg("qlens"), py::arg("scale") = py::none(),
+      py::arg("device") = 0,
+      "o (Tq,Hq,128) float32: chunked-prefill (extend) attention over a paged KV "
+      "cache. The last qlens[b] of the lens[b] keys of sequence b are new tokens; q "
+      "(Tq,Hq,128) packs their queries, sequence after sequence, Tq = sum(qlens). "
+      "Token i of sequence b attends to the keys t <= lens[b] - qlens[b] + i. "
+      "k_pages, v_pages, table and lens as in attn_paged_decode (the new tokens' "
+      "keys are in the pool already); qlens (B,) integer in 1 .. lens[b]. "
+      "scale=None is 1/sqrt(128). TypeError on a floating table, lens or qlens, "
+      "ValueError on an unsupported shape, length, table entry, qlens that do not "
+      "sum to Tq or a non-finite input, all before any device work");
+
+  m.def(
+      "attn_extend_plan",
+      [](py::object qlens_, int group) {
+        auto arr = paged_ints("attn_extend_plan", "qlens", qlens_, 1);
+        if (arr.shape(0) < 1 || arr.shape(0) > 65535)
+          throw py::value_error("attn_extend_plan: qlens must hold 1 .. 65535 lengths");
+        const std::vector<int> qlens = paged_narrow(arr);
+        const payload::AttnExtendPlan plan = payload::attn_extend_plan(
+            qlens.data(), static_cast<int>(qlens.size()), group);
+        py::array_t<int32_t> items({static_cast<py::ssize_t>(plan.items.size() / 2),
+                                    py::ssize_t{2}});
+        py::array_t<int32_t> cu(static_cast<py::ssize_t>(qlens.size()));
+        std::copy(plan.items.begin(), plan.items.end(), items.mutable_data());
+        std::copy(plan.cu.begin(), plan.cu.end(), cu.mutable_data());
+        return py::make_tuple(items, cu);
+      },
+      py::arg("qlens"), py::arg("group"),
+      "the work plan of the extend kernel, computed on the host with the arithmetic "
+      "of the device's plan kernel: (items int32 (n,2) of (sequence, first column) "
+      "over blocks of 128 of a sequence's qlens[b] * group (token, head) columns, "
+      "cu int32 (B,) of a sequence's first token in the packed q); n <= "
+      "ceil(sum(qlens) * group / 128) + B, group in 1 .. 16; host only, no GPU");
+
+  m.def(
+      "run_attn_extend_check",
+      [](int batch, int hq, int hkv, int length, int page, int device) {
+        payload::attn_paged_shape(batch, hq, hkv, page, 1, 1);
+        if (length < 1 || length > payload::kExtendMaxLen)
+          throw py::value_error("run_attn_extend_check: length must be in 1 .. 2^24");
+        payload::AttnCheck r;
+        {
+          py::gil_scoped_release rel;
+          r = payload::run_attn_extend_check(batch, hq, hkv, length, page, device);
+        }
+        return attn_check_dict(r);
+      },
+      py::arg("batch"), py::arg("hq"), py::arg("hkv"), py::arg("length"),
+      py::arg("page") = 64, py::arg("device") = 0,
+      "extend attention self-check on the ragged lengths of run_attn_paged_check and "
+      "runs of new tokens that cycle through (1, the whole length, 17, an odd "
+      "prefix), under a scrambled table with NaN in the unreferenced pages: max_err "
+      "of prefill's selection pattern (expect exactly 0) and max_rel = max |o - fp64 "
+      "ref| / max |v| of a dense pattern (expect <= 2^-8)");
+
+  m.def(
+      "run_attn_extend",
+      [](int batch, int hq, int hkv, int length, int new_tokens, int page, int iters,
+         bool ragged, int device) {
+        payload::attn_paged_shape(batch, hq, hkv, page, 1, 1);
+        if (iters < 1) throw py::value_error("run_attn_extend: iters must be >= 1");
+        payload::AttnExtendResult r;
+        {
+          py::gil_scoped_release rel;
+          r = payload::run_attn_extend(batch, hq, hkv, length, new_tokens, page, iters,
+                                       ragged, device);
+        }
+        py::dict d = attn_timed_dict(batch, hq, hkv, length, iters);
+        d["new"] = new_tokens;
+        d["page"] = page;
+        d["ragged"] = ragged;
+        d["items"] = r.items;
+        d["tflops"] = r.tflops;
+        d["tok_per_s"] = r.tok_per_s;
+        d["max_rel"] = r.max_rel;
+        return d;
+      },
+      py::arg("batch") = 8, py::arg("hq") = 64, py::arg("hkv") = 8,
+      py::arg("length") = 4096, py::arg("new_tokens") = 1024, py::arg("page") = 64,
+      py::arg("iters") = 10, py::arg("ragged") = false, py::arg("device") = 0,
+      "timed extend attention: the last min(new_tokens, len) keys of every sequence "
+      "are new tokens; pool and q filled on the device with the dense hash pattern "
+      "through a fixed scrambled table; plan and extend per launch; TFLOP/s over "
+      "the unmasked pairs only, tok_per_s over the new tokens, 16 spread output "
+      "rows checked against fp64; ragged=True gives every eighth sequence `length` "
+      "keys and the rest length/8; items is the plan's item count");
 }

@@ -107,6 +107,13 @@ read, then a timed run beside the bf16 kernel) and `judge_paged8` fails
 Nothing else puts 8-bit loads and the fp8 conversion instructions in front of
 the matrix cores. `quant_rel`, the error of the format itself, is carried and
 never judged.
+
+And so has the step between decode and a cold prompt. `run_extend` runs
+`instaslice-payload extend` (chunked prefill: a run of new tokens per sequence
+over the paged cache and, causally, each other; the pool's chunk images found
+through the block table and staged through LDS for 128 query columns, bound by
+the matrix cores) and `judge_extend` fails "extend" on `judge_paged`'s terms
+for `max_err`, `max_rel` and `page`, with `new` among the counts.
 """
 
 from __future__ import annotations
@@ -570,4 +577,33 @@ def run_prefill(profile_name: str, env: Optional[Dict[str, str]] = None,
     parse_profile_name(profile_name)
     return _run_child(profile_name, ["prefill"], CHILD_TIMEOUT_S, "max_err",
                       lambda report: judge_prefill(report, profile_name),
+                      env, runner)
+
+
+# ---- extend -----------------------------------------------------------------
+
+def judge_extend(report: dict, profile_name: str) -> dict:
+    """Judge an `instaslice-payload extend` report: "extend" fails unless
+    `max_err` is a numeric zero, `max_rel` is a real number in [0, 2**-8] (the
+    numerics contract is decode's, see ATTN_MAX_REL), `batch`, `hq`, `hkv`,
+    `len`, `new`, `iters`, `items` are integer counts >= 1 and `page` is 32,
+    64, 128 or 256. `tflops` and `tok_per_s` are carried and never judged.
+    Pure; the report's own `ok` is not trusted. ValueError on a profile name
+    that does not parse."""
+    return _judge_one(report, profile_name, "extend",
+                      lambda r: _attn_fields_clean(r, ATTN_MAX_REL)
+                      and _counts_from_one(r, ("new", "items"))
+                      and _is_count(r.get("page")) and r["page"] in PAGED_PAGES)
+
+
+def run_extend(profile_name: str, env: Optional[Dict[str, str]] = None,
+               runner: Callable = subprocess.run) -> dict:
+    """Run `instaslice-payload extend` (default shape, run of new tokens, page
+    size and iterations) in a fresh child with `env` and judge its report,
+    with the same contract as `run_paged`: every way the child can fail comes
+    back as `ok: False` with a `reason`, and only an unparseable profile name
+    raises (ValueError)."""
+    parse_profile_name(profile_name)
+    return _run_child(profile_name, ["extend"], CHILD_TIMEOUT_S, "max_err",
+                      lambda report: judge_extend(report, profile_name),
                       env, runner)
